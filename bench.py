@@ -12,7 +12,12 @@ Other workloads (`--workload`): `ntt` (forward + inverse negacyclic NTT, N = 2^1
 `keyswitch` (BASELINE configs[3]: N = 2^16, L = 16, K = 4, dnum = 4, limbs sharded across the
 ranks with one RCCL all-gather of INTT(d2) per key-switch).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel of the workload, timed per
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly `--steps` steps and
+prints the headline (`metric`, `value`, `unit`, `ms_per_step`, the configuration); with
+`--dump-outputs DIR` it also writes what the last timed step computed.  Everything else is behind
+`--full`: the per-kernel pass and the rooflines, the ride-along legs (NTTs/sec, key-switch), the
+live rocprofv3 counter passes, the comparison timings of the rotation workloads, the dist_check
+and the cpu_baseline.  There, `roofline` is for the dominant kernel of the workload, timed per
 launch with HIP events that libfhecore records on the launch stream (fhe_prof_begin/end);
 `achieved` = its algorithmic bytes per launch / its mean launch time.  `cpu_baseline` is the exact
 C restatement in oracle/ (OpenMP), run on rank 0 at N = 1 over a bounded sample.
@@ -38,6 +43,9 @@ from fhecore import dist as fdist  # noqa: E402
 from fhecore._capi import check, load  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
+# a plain hommult run's untimed load before its warmup: the chip ramps its clock up over the first
+# ~50 ms of sustained load, and the NTT leg that --full runs first (~0.15 s) is not there to do it
+HOMMULT_PREHEAT_S = 0.2
 METRIC = "NTTs/sec + HomMult/sec at N=2^16, 8 RNS limbs; achieved HBM GB/s vs peak"
 
 
@@ -74,6 +82,15 @@ def parse():
                          "instead of the forward")
     ap.add_argument("--no-keyswitch-leg", action="store_true",
                     help="hommult: skip the key-switch ride-along leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: per-kernel times "
+                         "and rooflines, the ride-along legs, live counter passes, comparison "
+                         "timings, dist_check, cpu_baseline (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as "
+                         "DIR/<name>_lo32.npy and DIR/<name>_hi32.npy (float64: the low and high "
+                         "32 bits of each u64 word, exact); outputs above the size cap are "
+                         "sampled at fixed seeded positions")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="cpu_baseline sample budget")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dist-check", action="store_true",
@@ -82,7 +99,10 @@ def parse():
     ap.add_argument("--no-pmc", action="store_true",
                     help="hommult: skip the live rocprofv3 traffic passes (roofline.traffic then "
                          "falls back to the committed profiles/hbm_traffic.json)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps only
+        args.no_cpu_baseline = args.no_dist_check = args.no_pmc = args.no_keyswitch_leg = True
+    return args
 
 
 def dist_setup(args):
@@ -128,12 +148,35 @@ def uniform_limbs(gen, moduli, lead, n):
     return torch.cat(parts, dim=len(lead)).contiguous()
 
 
-def timed(fn, args, world, max_marks):
+DUMP_WORDS = 1 << 21  # words written per run by --dump-outputs: 2 x 8 B each = 32 MiB of .npy
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: the int64 device tensors `arrays` {name: tensor} as path/<name>_lo32.npy and
+    path/<name>_hi32.npy (float64, the low and high 32 bits of every word: exact, where a float64
+    of the whole 60-bit residue would round).  The run's DUMP_WORDS are split evenly over the
+    arrays; a larger array is sampled at sorted positions drawn from a fixed seed, the same in
+    every run.  Ranks above 0 of a multi-GPU run append .rank<r> to the name."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_WORDS // max(len(arrays), 1)
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            pos = np.sort(np.random.default_rng(2024).integers(0, flat.numel(), cap))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        w = flat.cpu().numpy().view(np.uint64)
+        tag = name if world == 1 else f"{name}.rank{rank}"
+        np.save(os.path.join(path, tag + "_lo32.npy"), (w & 0xFFFFFFFF).astype(np.float64))
+        np.save(os.path.join(path, tag + "_hi32.npy"), (w >> 32).astype(np.float64))
+
+
+def timed(fn, args, world, max_marks, outputs=None):
     """Warmup, then exactly `steps` calls between barrier+sync brackets with nothing else on the
-    stream; then the same `steps` calls again with a HIP-event mark after each launch group, whose
-    averages are the per-kernel durations (kernel_ms, roofline.achieved).  The marks stay out of
-    the timed window: each record costs ~4 us of idle GPU between kernels (rocprofv3 trace,
-    DESIGN.md §6)."""
+    stream; `outputs()` names what the last of them computed, for --dump-outputs.  With --full,
+    the same `steps` calls then run again with a HIP-event mark after each launch group, whose
+    averages are the per-kernel durations (kernel_ms, roofline.achieved); without it the second
+    value returned is empty.  The marks stay out of the timed window: each record costs ~4 us of
+    idle GPU between kernels (rocprofv3 trace)."""
     for _ in range(args.warmup):
         fn()
     barrier(world)
@@ -142,6 +185,11 @@ def timed(fn, args, world, max_marks):
         fn()
     barrier(world)
     dt = time.perf_counter() - t0
+    if outputs is not None and getattr(args, "dump_outputs", None):
+        rank = torch.distributed.get_rank() if world > 1 else 0
+        dump_outputs(args.dump_outputs, outputs(), rank, world)
+    if not args.full:
+        return max_over_ranks(dt, world), {}
     lib = load()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     check(lib.fhe_prof_begin(max_marks, stream), "fhe_prof_begin")
@@ -504,7 +552,9 @@ def run_hommult(args, world, rank):
     Order: everything is allocated first; the NTT leg runs first (it also brings the chip to its
     sustained clock, which the driver's short --warmup would otherwise leave inside the timed
     region: DESIGN.md §8 "Warmup matters"), then the HomMult leg (W warmup + exactly K timed
-    steps), then the key-switch leg."""
+    steps), then the key-switch leg.  A plain run (no --full) has neither leg: it brings the chip to
+    its sustained clock with HOMMULT_PREHEAT_S of the HomMult step itself, so that `value` reads
+    the same sustained rate, and then times the K steps."""
     L = 8
     shard = fdist.LimbShard(L, world, rank)
     n = 1 << args.log_n
@@ -523,22 +573,25 @@ def run_hommult(args, world, rank):
     # poly-limbs per GPU (64 polys x 8 limbs at N = 1; the same count of this rank's limbs above, so
     # per-GPU work stays fixed like the HomMult leg's), sustained, every NTT counted
     npolys = 64 * L // max(shard.nlimbs, 1)
-    x = uniform_limbs(gen, mods, (npolys,), n)
+    if args.full:
+        x = uniform_limbs(gen, mods, (npolys,), n)
 
-    def ntt_pair():
-        ctx.ntt_(x, limb0=shard.lo)
-        ctx.intt_(x, limb0=shard.lo)
+        def ntt_pair():
+            ctx.ntt_(x, limb0=shard.lo)
+            ctx.intt_(x, limb0=shard.lo)
 
-    nargs = argparse.Namespace(warmup=100, steps=200)
-    ntt_dt, ntt_k = timed(ntt_pair, nargs, world, 8 * nargs.steps + 8)
-    ntt_per_s = 2 * npolys * shard.nlimbs * world * nargs.steps / ntt_dt
+        nargs = argparse.Namespace(warmup=100, steps=200, full=True)
+        ntt_dt, ntt_k = timed(ntt_pair, nargs, world, 8 * nargs.steps + 8)
+        ntt_per_s = 2 * npolys * shard.nlimbs * world * nargs.steps / ntt_dt
+    else:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < HOMMULT_PREHEAT_S:
+            step()
+            torch.cuda.synchronize()
 
-    dt, kavg = timed(step, args, world, 8 * args.steps + 8)
+    dt, kavg = timed(step, args, world, 8 * args.steps + 8, outputs=lambda: {"d": d})
     hm_per_s = gbatch * args.steps / dt  # each rank covers its limbs of all gbatch pairs
-    shape = {"log_n": args.log_n, "batch": gbatch, "nlimbs": shard.nlimbs}
-    # dominant kernel: reads 4 and writes 3 polynomials of this rank's limbs = algorithmic traffic
-    dom = "hm_row_tensor"
-    alg = gbatch * 7 * shard.nlimbs * n * 8
     pipe_gbps = hm_per_s * 7 * L * n * 8 / 1e9 / world
     out = {
         "metric": METRIC, "value": round(hm_per_s, 2), "unit": "HomMult/s",
@@ -546,16 +599,27 @@ def run_hommult(args, world, rank):
         "config": {"workload": "hommult ct x ct (NTT -> tensor -> INTT), BASELINE configs[2]",
                    "log_n": args.log_n, "limbs": L, "batch_per_gpu": args.batch,
                    "global_batch": gbatch, "parallelism": f"rns-limb-shard x{world}"},
+        "hommult_pipeline_hbm_gbps_per_gpu": round(pipe_gbps, 1),
+        "hommult_pipeline_frac_of_peak": round(pipe_gbps / HBM_PEAK_GBPS, 4),
+    }
+    if args.bits != 60:
+        out["config"]["modulus_bits"] = args.bits
+    if not args.full:
+        out["preheat_s"] = HOMMULT_PREHEAT_S
+        return out, None
+    shape = {"log_n": args.log_n, "batch": gbatch, "nlimbs": shard.nlimbs}
+    # dominant kernel: reads 4 and writes 3 polynomials of this rank's limbs = algorithmic traffic
+    dom = "hm_row_tensor"
+    alg = gbatch * 7 * shard.nlimbs * n * 8
+    out.update({
         "ntt_per_sec": round(ntt_per_s, 1),
         "ntt_config": {"log_n": args.log_n, "direction": "forward+inverse", "polys_per_gpu": npolys,
                        "limbs_per_gpu": shard.nlimbs, "warmup": nargs.warmup,
                        "steps": nargs.steps, "order": "run before the HomMult leg"},
         "ntt_kernel_ms": {k: round(v, 4) for k, v in ntt_k.items()},
-        "hommult_pipeline_hbm_gbps_per_gpu": round(pipe_gbps, 1),
-        "hommult_pipeline_frac_of_peak": round(pipe_gbps / HBM_PEAK_GBPS, 4),
         "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
         "roofline": roofline(dom, alg, kavg.get(dom, float("nan")), shape),
-    }
+    })
     # algorithmic bytes exclude the twiddles (cache-resident), reported separately:
     # the forward and inverse row tables of this rank's limbs, (w, w') pairs of 16 B, N per limb
     tw = 2 * shard.nlimbs * n * 16
@@ -577,8 +641,6 @@ def run_hommult(args, world, rank):
                                                    sum(kavg.values()))
     out["limiter"] = "valu" if out.get("roofline_alu", {}).get("frac", 0) > \
         out["roofline"]["frac"] else "hbm"
-    if args.bits != 60:
-        out["config"]["modulus_bits"] = args.bits
     # HBM traffic of the dominant kernel measured in this run (rank 0 of a one-GPU job only: the
     # profiled child shares the GPU); the committed figure stays beside it for comparison
     if rank == 0 and world == 1 and not args.no_pmc and args.bits == 60:
@@ -601,7 +663,7 @@ def run_hommult(args, world, rank):
     if not (args.no_keyswitch_leg or args.bits != 60):
         def ks_leg():
             legs["ks"] = KeyswitchLeg(args, world, rank)
-            return legs["ks"].run(argparse.Namespace(warmup=20, steps=50))
+            return legs["ks"].run(argparse.Namespace(warmup=20, steps=50, full=True))
 
         out["keyswitch_leg"] = guarded_leg(ks_leg, out, rank, "keyswitch_leg")
         # the profiled child pass runs outside the watchdog: it has its own time limit, after
@@ -654,7 +716,8 @@ def run_vec(args, world, rank):
                      shard.nlimbs, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                   "fhe_vec")
 
-    dt, kavg = timed(step, args, world, 8 * args.steps + 8)
+    dt, kavg = timed(step, args, world, 8 * args.steps + 8,
+                     outputs=lambda: {op: s[2] for op, s in zip(("add", "sub", "mul"), sets)})
     coeffs = polys * shard.nlimbs * n
     per_op = coeffs * 24
     ops_per_s = 3 * coeffs * world * args.steps / dt
@@ -667,8 +730,10 @@ def run_vec(args, world, rank):
                 "kernel_ms": {k: round(v, 4) for k, v in kavg.items()}}
     for k, v in kavg.items():
         out_line["roofline_" + k] = roofline(k, per_op, v, {"log_n": args.log_n, "polys": polys})
-    dom = max(kavg, key=kavg.get)
-    out_line["roofline"] = roofline(dom, per_op, kavg[dom], {"log_n": args.log_n, "polys": polys})
+    if kavg:
+        dom = max(kavg, key=kavg.get)
+        out_line["roofline"] = roofline(dom, per_op, kavg[dom],
+                                        {"log_n": args.log_n, "polys": polys})
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_vec(ctx.moduli, args.log_n, args.cpu_seconds)
@@ -736,21 +801,24 @@ def run_ntt(args, world, rank):
         ctx.ntt_(x, limb0=shard.lo)
         ctx.intt_(x, limb0=shard.lo)
 
-    dt, kavg = timed(step, args, world, 8 * args.steps + 8)
+    dt, kavg = timed(step, args, world, 8 * args.steps + 8, outputs=lambda: {"x": x})
     ntts = 2 * polys * shard.nlimbs * world * args.steps
-    dom = max(kavg, key=kavg.get)
-    shape = {"log_n": args.log_n, "polys": polys, "nlimbs": shard.nlimbs}
     out = {"metric": METRIC, "value": round(ntts / dt, 1), "unit": "NTT/s",
            "ms_per_step": round(dt / args.steps * 1e3, 4),
            "config": {"workload": "forward+inverse NTT, single-limb transforms", "log_n": args.log_n,
-                      "limbs": L, "polys_per_gpu": polys, "parallelism": f"rns-limb-shard x{world}"},
+                      "limbs": L, "polys_per_gpu": polys, "parallelism": f"rns-limb-shard x{world}"}}
+    if not args.full:
+        return out, None
+    dom = max(kavg, key=kavg.get)
+    shape = {"log_n": args.log_n, "polys": polys, "nlimbs": shard.nlimbs}
+    out.update({
            "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
            # the whole transform: one NTT reads and writes each coefficient once (16 B per
            # coefficient per direction), over the summed time of its column and row passes
            "roofline": transform_roofline(kavg, 2 * polys * shard.nlimbs * n * 16, shape),
            # each pass alone (every pass moves the data once more)
            "roofline_passes": {k: roofline(k, polys * shard.nlimbs * n * 16, v, shape)
-                               for k, v in kavg.items()}}
+                               for k, v in kavg.items()}})
     # butterflies of the dominant pass: row passes run the last log R2 stages, column passes the
     # first log R1
     pb = polys * shard.nlimbs * (row_bflies(args.log_n) if "row" in dom
@@ -844,7 +912,7 @@ def run_ntt_batch(args, world, rank):
     # timing it on uniform inputs is the round trip's second half)
     inv = bool(getattr(args, "inverse", False))
     step = (lambda: ctx.intt_(x)) if inv else (lambda: ctx.ntt_(x))  # noqa: E731
-    dt, kavg = timed(step, args, world, 4 * args.steps + 4)
+    dt, kavg = timed(step, args, world, 4 * args.steps + 4, outputs=lambda: {"x": x})
     ntts = P * L * args.steps
     shape = {"log_n": log_n, "polys": mine, "nlimbs": L}
     per_pass = mine * L * n * 16
@@ -856,10 +924,12 @@ def run_ntt_batch(args, world, rank):
                       "limbs": L, "polys": P, "polys_per_gpu": mine,
                       "parallelism": f"poly-shard x{world}"},
            # whole transform: read + write every coefficient once (two passes move it twice)
-           "ntt_alg_hbm_gbps_per_gpu": round(ntts / world / dt * n * 16 / 1e9, 1),
+           "ntt_alg_hbm_gbps_per_gpu": round(ntts / world / dt * n * 16 / 1e9, 1)}
+    if args.full:
+        out.update({
            "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
            "roofline": transform_roofline(kavg, per_pass, shape),
-           "roofline_passes": {k: roofline(k, per_pass, v, shape) for k, v in kavg.items()}}
+           "roofline_passes": {k: roofline(k, per_pass, v, shape) for k, v in kavg.items()}})
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_ntt(ctx.moduli[:8], log_n, args.cpu_seconds)
@@ -950,16 +1020,17 @@ class KeyswitchLeg:
 
     def step(self):
         if self.native:
-            self.ctx.keyswitch_dist(self.comm, self.d2, self.evk_b, self.evk_a,
-                                    chunks=self.chunks, workspace=self.ws)
+            self.last = self.ctx.keyswitch_dist(self.comm, self.d2, self.evk_b, self.evk_a,
+                                                chunks=self.chunks, workspace=self.ws)
         else:
-            fdist.sharded_keyswitch(self.ctx, self.d2, self.evk_b, self.evk_a, self.shard,
-                                    group=self.group)
+            self.last = fdist.sharded_keyswitch(self.ctx, self.d2, self.evk_b, self.evk_a,
+                                                self.shard, group=self.group)
 
     def run(self, targs, valu=False):
         L, K, dnum, B, world = self.L, self.K, self.DNUM, self.B, self.world
         n = 1 << self.log_n
-        dt, kavg = timed(self.step, targs, world, 64 * targs.steps + 64)
+        dt, kavg = timed(self.step, targs, world, 64 * targs.steps + 64,
+                         outputs=lambda: {"ks0": self.last[0], "ks1": self.last[1]})
         gather = self.comm.gather_ms() if self.native else []  # the last call's chunks
         ks_per_s = B * targs.steps / dt
         ms_per_ks = dt / (B * targs.steps) * 1e3
@@ -988,6 +1059,8 @@ class KeyswitchLeg:
                                  self.chunks if self.native else 1).plan
         # what each rank ends up with (its group's g blocks; nothing is gathered at g = 1)
         res["gather_bytes_per_chunk"] = plan.block_words * 8 * self.g if self.g > 1 else 0
+        if not targs.full:
+            return res
         # integer-ALU roofline of one key-switch on this rank, butterflies only: INTT of the own
         # d2 limbs; ModUp: every digit's extended rows = dnum (nl + K) - nl forward NTTs; ModDown:
         # INTT of the 2 K special rows, forward NTT of the 2 nl converted rows
@@ -1114,7 +1187,7 @@ def run_mulrelin(args, world, rank):
         ctx.mul_relin(a, b, kb, ka, rescale=True, workspace=ws, out=out)  # eager once
         with fc.Graph() as g:
             ctx.mul_relin(a, b, kb, ka, rescale=True, workspace=ws, out=out)
-        dt, kavg = timed(g.launch, args, world, 4)
+        dt, kavg = timed(g.launch, args, world, 4, outputs=lambda: {"out": out})
     per_s = B * args.steps * world / dt
     # per multiply: read 2 cts (4 L limbs), the key once per batch, write 2 (L-1) limbs
     alg = (B * (4 * L + 2 * (L - 1)) + dnum * 2 * (L + K)) * n * 8 // B
@@ -1202,15 +1275,18 @@ def run_rotate(args, world, rank):
         for r in range(R):
             ctx.rotate(ct, elts[r], keys[r][0], keys[r][1], workspace=ws)
 
-    dt, kavg = timed(hoisted, args, world, 64)
-    dt_plain, _ = timed(plain, args, world, 1)
+    dt, kavg = timed(hoisted, args, world, 64, outputs=lambda: {"out": out})
     per_s = B * R * args.steps * world / dt
-    return {"metric": "hoisted rotations/sec at N=2^16, L=16, K=4, dnum=4 (8 Galois elements per ModUp)",
+    line = {"metric": "hoisted rotations/sec at N=2^16, L=16, K=4, dnum=4 (8 Galois elements per ModUp)",
             "value": round(per_s, 2), "unit": "rotations/s",
             "ms_per_step": round(dt / args.steps * 1e3, 4),
             "config": {"workload": "hoisted rotations (fhe_rotate_hoisted)", "log_n": args.log_n,
                        "L": L, "K": K, "dnum": dnum, "rotations_per_modup": R, "batch": B,
-                       "parallelism": f"replicas x{world}"},
+                       "parallelism": f"replicas x{world}"}}
+    if not args.full:
+        return line, None
+    dt_plain, _ = timed(plain, args, world, 1)
+    line.update({
             "unhoisted_rotations_per_sec": round(B * R * args.steps * world / dt_plain, 2),
             "hoisting_speedup": round(dt_plain / dt, 3),
             "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
@@ -1224,7 +1300,8 @@ def run_rotate(args, world, rank):
             "roofline_inner_product": roofline(
                 "ks_inner (gathered inner product, per launch)",
                 (dnum * B * (L + K) + 2 * dnum * (L + K) + 2 * B * (L + K)) * n * 8,
-                kavg.get("ks_inner", float("nan")), {"log_n": args.log_n, "L": L, "B": B})}, (
+                kavg.get("ks_inner", float("nan")), {"log_n": args.log_n, "L": L, "B": B})})
+    return line, (
         cpu_baseline_rotate(ctx.moduli, ctx.special, args.log_n, dnum, args.cpu_seconds)
         if rank == 0 and world == 1 and not args.no_cpu_baseline else None)
 
@@ -1295,11 +1372,12 @@ def run_rotsum(args, world, rank):
                            lib.fhe_rotate_hoisted_workspace(ctx.handle, B)))
     out = torch.empty(B, 2, L, n, dtype=torch.int64, device="cuda")
     fused = lambda: ctx.rotate_sum_hoisted(ct, elts, keys, pts, workspace=ws, out=out)  # noqa: E731
-    # the single-hoisted composition: the plaintexts broadcast over the batch (Q rows only)
-    rot = torch.empty(R - 1, B, 2, L, n, dtype=torch.int64, device="cuda")
-    ptq = [p[:L].expand(B, 2, L, n).contiguous() for p in pts]
-    prod = torch.empty(B, 2, L, n, dtype=torch.int64, device="cuda")
-    acc = torch.empty(B, 2, L, n, dtype=torch.int64, device="cuda")
+    if args.full:
+        # the single-hoisted composition: the plaintexts broadcast over the batch (Q rows only)
+        rot = torch.empty(R - 1, B, 2, L, n, dtype=torch.int64, device="cuda")
+        ptq = [p[:L].expand(B, 2, L, n).contiguous() for p in pts]
+        prod = torch.empty(B, 2, L, n, dtype=torch.int64, device="cuda")
+        acc = torch.empty(B, 2, L, n, dtype=torch.int64, device="cuda")
 
     def single():
         ctx.rotate_hoisted(ct, elts[1:], keys[1:], workspace=ws, out=rot)
@@ -1308,21 +1386,24 @@ def run_rotsum(args, world, rank):
             ctx.vec("mul", rot[r - 1], ptq[r], out=prod)
             ctx.vec("add", acc, prod, out=acc)
 
-    dt, kavg = timed(fused, args, world, 64)
-    dt_single, _ = timed(single, args, world, 1)
-    del rot, ptq, prod, acc
+    dt, kavg = timed(fused, args, world, 64, outputs=lambda: {"out": out})
     per_s = B * R * args.steps * world / dt
-    # per call: read the batch's cts (2 L limbs each) and write the sums (2 L), every key
-    # ((R - 1) dnum 2 (L + K) limbs) and plaintext (R (L + K)) once per batch
-    alg_call = (B * 4 * L + (R - 1) * dnum * 2 * (L + K) + R * (L + K)) * n * 8
-    return {"metric": "rotation-sum terms/sec at N=2^16, L=16, K=4, dnum=4 (8 terms per ModUp "
+    line = {"metric": "rotation-sum terms/sec at N=2^16, L=16, K=4, dnum=4 (8 terms per ModUp "
                       "and per ModDown, double hoisting)",
             "value": round(per_s, 2), "unit": "terms/s",
             "ms_per_step": round(dt / args.steps * 1e3, 4),
             "config": {"workload": "double-hoisted rotation sum (fhe_rotate_sum_hoisted)",
                        "log_n": args.log_n, "L": L, "K": K, "dnum": dnum, "terms": R,
                        "rotations": R - 1, "batch": B, "parallelism": f"replicas x{world}"},
-            "rotsums_per_sec": round(B * args.steps * world / dt, 2),
+            "rotsums_per_sec": round(B * args.steps * world / dt, 2)}
+    if not args.full:
+        return line, None
+    dt_single, _ = timed(single, args, world, 1)
+    del rot, ptq, prod, acc
+    # per call: read the batch's cts (2 L limbs each) and write the sums (2 L), every key
+    # ((R - 1) dnum 2 (L + K) limbs) and plaintext (R (L + K)) once per batch
+    alg_call = (B * 4 * L + (R - 1) * dnum * 2 * (L + K) + R * (L + K)) * n * 8
+    line.update({
             "single_hoisted_terms_per_sec": round(B * R * args.steps * world / dt_single, 2),
             "double_hoisting_speedup": round(dt_single / dt, 3),
             "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
@@ -1336,7 +1417,8 @@ def run_rotsum(args, world, rank):
                 "rot_sum (gathered inner products x plaintexts, per launch)",
                 (R * ((dnum - 1) * B * (L + K) + B * 2 * L + 2 * dnum * (L + K) + (L + K)) +
                  2 * B * (L + K) + 2 * B * L) * n * 8,
-                kavg.get("rot_sum", float("nan")), {"log_n": args.log_n, "L": L, "B": B})}, None
+                kavg.get("rot_sum", float("nan")), {"log_n": args.log_n, "L": L, "B": B})})
+    return line, None
 
 
 def run_lintrans(args, world, rank):
@@ -1366,9 +1448,20 @@ def run_lintrans(args, world, rank):
     out = torch.empty(B, 2, L, n, dtype=torch.int64, device="cuda")
     fused = lambda: ctx.linear_transform(ct, baby, bkeys, giant, gkeys, pts, workspace=ws,  # noqa: E731
                                          out=out)
-    dt, kavg = timed(fused, args, world, 128)
-    # the hoisted diagonal method: sum_i diag_i rot_i(ct), i < n1 n2, one ModUp for the rotations
+    dt, kavg = timed(fused, args, world, 128, outputs=lambda: {"out": out})
     D = n1 * n2
+    per_s = B * args.steps * world / dt
+    line = {"metric": "BSGS linear transforms/sec at N=2^16, L=16, K=4, dnum=4 (16 diagonals: "
+                      "4 baby x 4 giant steps, double hoisting)",
+            "value": round(per_s, 2), "unit": "transforms/s",
+            "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "config": {"workload": "BSGS linear transform (fhe_linear_transform)",
+                       "log_n": args.log_n, "L": L, "K": K, "dnum": dnum, "n1": n1, "n2": n2,
+                       "diagonals": D, "batch": B, "parallelism": f"replicas x{world}"},
+            "diagonals_per_sec": round(D * per_s, 2)}
+    if not args.full:
+        return line, None
+    # the hoisted diagonal method: sum_i diag_i rot_i(ct), i < n1 n2, one ModUp for the rotations
     elts = [ctx.galois_elt(i) for i in range(1, D)]
     keys = [key() for _ in range(1, D)]
     rot = torch.empty(D - 1, B, 2, L, n, dtype=torch.int64, device="cuda")
@@ -1386,23 +1479,16 @@ def run_lintrans(args, world, rank):
 
     dt_diag, _ = timed(diagonal, args, world, 1)
     del rot, diag, prod, acc
-    per_s = B * args.steps * world / dt
     # per call: read the cts (2 L limbs each), write the results (2 L); every key ((n1 - 1) +
     # (n2 - 1) rotation keys of dnum 2 (L + K) limbs) and diagonal (n1 n2 (L + K)) once per batch
     alg_call = (B * 4 * L + (n1 + n2 - 2) * dnum * 2 * (L + K) + D * (L + K)) * n * 8
-    return {"metric": "BSGS linear transforms/sec at N=2^16, L=16, K=4, dnum=4 (16 diagonals: "
-                      "4 baby x 4 giant steps, double hoisting)",
-            "value": round(per_s, 2), "unit": "transforms/s",
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "config": {"workload": "BSGS linear transform (fhe_linear_transform)",
-                       "log_n": args.log_n, "L": L, "K": K, "dnum": dnum, "n1": n1, "n2": n2,
-                       "diagonals": D, "batch": B, "parallelism": f"replicas x{world}"},
-            "diagonals_per_sec": round(D * per_s, 2),
+    line.update({
             "hoisted_diagonal_method_per_sec": round(B * args.steps * world / dt_diag, 2),
             "bsgs_speedup": round(dt_diag / dt, 3),
             "kernel_ms": {k: round(v, 4) for k, v in kavg.items()},
             "roofline": roofline("linear transform (whole call, per GPU)", alg_call,
-                                 dt / args.steps * 1e3, {"log_n": args.log_n, "L": L, "B": B})}, None
+                                 dt / args.steps * 1e3, {"log_n": args.log_n, "L": L, "B": B})})
+    return line, None
 
 
 def shard_mismatches(got, ref_full, shard) -> int:
@@ -1523,10 +1609,14 @@ def emit_line(out, cpu):
             "data": "synthetic (uniform residues per RNS limb, seeded)",
             "config": out.pop("config")}
     line.update(out)
+    full = getattr(args, "full", True)
+    line["full"] = full
+    if not line.get("kernel_ms", True):
+        del line["kernel_ms"]  # a plain run has no per-kernel pass
     # why the live rocprofv3 passes did not run, at the top level of the line (the per-roofline
     # *_live_error fields say it again where the committed profiles stand in)
     skip = "--no-pmc" if getattr(args, "no_pmc", False) else profiled_parent()
-    if skip:
+    if skip and full:
         line["pmc_skipped"] = skip
     line["cpu_baseline"] = cpu
     sys.stdout.flush()

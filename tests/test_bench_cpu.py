@@ -311,3 +311,54 @@ def test_keyswitch_design_minimum_bytes():
     assert b == 5989466112
     assert 6046000000 / b < 1.01
     assert bench.ks_design_min_bytes(32, 2, 16, 4, 4, 1 << 16) < b / 3
+
+
+def test_plain_run_switches_everything_beside_the_steps_off(monkeypatch):
+    """Without --full the parsed arguments ask for no cpu_baseline, dist_check, counter pass or
+    key-switch leg, and timed() runs no per-kernel pass; --full leaves each to its own switch."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    assert a.no_cpu_baseline and a.no_dist_check and a.no_pmc and a.no_keyswitch_leg
+    calls = []
+    monkeypatch.setattr(bench, "barrier", lambda world: None)
+    monkeypatch.setattr(bench, "load", lambda: pytest.fail("a plain run opened the profiler"))
+    dt, kavg = bench.timed(lambda: calls.append(1), a, 1, 64)
+    assert len(calls) == 2 + 7 and kavg == {} and dt >= 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-pmc"])
+    a = bench.parse()
+    assert a.full and a.no_pmc
+    assert not (a.no_cpu_baseline or a.no_dist_check or a.no_keyswitch_leg)
+
+
+def test_dump_outputs_is_exact_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): every 64-bit word comes back exactly from its two
+    float64 halves, words with bit 63 set included; an array above its share of DUMP_WORDS is
+    sampled at positions that are the same in every run; the files stay within the cap."""
+    import numpy as np
+
+    g = torch.Generator().manual_seed(3)
+    small = torch.randint(-2**63, 2**63 - 1, (3, 5, 7), generator=g, dtype=torch.int64)
+    small.view(-1)[0], small.view(-1)[1] = -1, 2**60 - 93
+    monkeypatch.setattr(bench, "DUMP_WORDS", 2 * 1000)
+    big = torch.randint(0, 2**60, (4321,), generator=g, dtype=torch.int64)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"small": small, "big": big})
+
+    def words(run, name):
+        lo, hi = (np.load(tmp_path / run / f"{name}_{h}32.npy") for h in ("lo", "hi"))
+        assert lo.dtype == hi.dtype == np.float64
+        return (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
+
+    assert sorted(os.listdir(tmp_path / "a")) == ["big_hi32.npy", "big_lo32.npy",
+                                                  "small_hi32.npy", "small_lo32.npy"]
+    assert (words("a", "small") == small.numpy().view(np.uint64).reshape(-1)).all()
+    sample = words("a", "big")
+    assert sample.shape == (1000,) and (sample == words("b", "big")).all()
+    pos = np.sort(np.random.default_rng(2024).integers(0, big.numel(), 1000))
+    assert (sample == big.numpy().view(np.uint64)[pos]).all()
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < \
+        16 * 2000 + 4 * 256
+    # the real cap: 2 float64 per word of DUMP_WORDS plus the .npy headers stays below 64 MB
+    monkeypatch.undo()
+    assert 16 * bench.DUMP_WORDS + 16 * 256 < 64 * 10**6

@@ -176,16 +176,17 @@ def test_bench_dist_check_native_world1(fc, chunks):
 
 
 def test_bench_default_line_end_to_end():
-    """bench.py as the driver runs it (one GPU, a short run): one JSON line carrying the headline,
-    the roofline, the key-switch leg and a bit-exact dist_check, and exit status 0."""
+    """bench.py --full (one GPU, a short run): one JSON line carrying the headline, the roofline,
+    the key-switch leg and a bit-exact dist_check, and exit status 0."""
     import json
     import os
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup",
-                        "1", "--batch", "8", "--ks-batch", "8", "--no-cpu-baseline", "--no-pmc"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3",
+                        "--warmup", "1", "--batch", "8", "--ks-batch", "8", "--no-cpu-baseline",
+                        "--no-pmc"],
                        capture_output=True, text=True, timeout=110, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -195,6 +196,54 @@ def test_bench_default_line_end_to_end():
     assert line["roofline"]["kernel"] == "hm_row_tensor" and line["roofline"]["frac"] > 0
     assert line["keyswitch_leg"]["value"] > 0
     assert line["dist_check"]["result"] == "bit-exact"
+
+
+def test_bench_plain_line_and_dumped_outputs(fc, tmp_path):
+    """A plain bench.py run (no --full): the headline fields and nothing that takes a run of its
+    own, exactly --steps timed steps, and --dump-outputs writes the last step's HomMult output --
+    here small enough to be written whole, so it is compared word for word with the oracle's
+    HomMult of the same seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import coracle
+    import torch
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+
+    log_n, batch = 12, 2
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps",
+                        "3", "--warmup", "1", "--batch", str(batch), "--log-n", str(log_n),
+                        "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=110, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["value"] > 0 and line["unit"] == "HomMult/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "u64" and line["steps"] == 3 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0 and line["full"] is False and line["cpu_baseline"] is None
+    assert abs(line["value"] - batch / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+    for moved in ("kernel_ms", "roofline", "ntt_per_sec", "keyswitch_leg", "dist_check",
+                  "roofline_alu", "roofline_valu"):
+        assert moved not in line
+    assert sorted(os.listdir(tmp_path)) == ["d_hi32.npy", "d_lo32.npy"]
+    lo, hi = (np.load(tmp_path / f"d_{h}32.npy") for h in ("lo", "hi"))
+    assert lo.dtype == hi.dtype == np.float64
+    got = (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
+    # the run's inputs again: the same seeded device generator, the same draws in the same order
+    ctx = fc.Context(log_n, L=8)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(1234)
+    a = bench.uniform_limbs(gen, ctx.moduli, (batch, 2), 1 << log_n)
+    b = bench.uniform_limbs(gen, ctx.moduli, (batch, 2), 1 << log_n)
+    ref = np.stack([coracle.hommult(fc.to_host(a[i]), fc.to_host(b[i]), ctx.moduli)
+                    for i in range(batch)])
+    assert got.shape == (ref.size,) and (got == ref.reshape(-1)).all()
 
 
 @pytest.mark.parametrize("log_n,G,groups,batch,chunks", [

@@ -7,7 +7,7 @@
 #   smoke                        __graft_entry__.smoke()                   -> <out>/smoke.log
 #   tests                        the whole GPU suite                       -> <out>/gputests.log
 #   tests=<path or -k expr>      a test file (path ending in .py) or a -k selection of the suite
-#   line:<tag>[=<bench args>]    one bench.py line                         -> <out>/bench_<tag>.json
+#   line:<tag>[=<bench args>]    one bench.py line (--full: legs, rooflines) -> <out>/bench_<tag>.json
 #   ab:<tag>=<reps>|<bench args>|<variant> ...   same-box A/B (tools/ab_bench.sh) -> <out>/ab_<tag>.txt
 #   bundle=A|B|R                 tools/round_bundle.sh part                -> <out>/
 #   prof:<tag>[=<bench args>]    tools/profile_round.sh of a bench command -> <out>/<tag>/
