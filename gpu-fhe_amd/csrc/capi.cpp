@@ -293,36 +293,55 @@ int fhe_keyswitch_shard(const fhe_ctx* c, uint64_t* ks0, uint64_t* ks1, const ui
                                 ws, hs(s));
 }
 
+// level in [1, L] for the *_level entry points (a null context fails in check_window first)
+static int check_level(const fhe_ctx* c, uint32_t level, const char* who) {
+  if (c && (level == 0 || level > c->L)) {
+    set_error(std::string(who) + ": level must be in [1, L]");
+    return kInvalid;
+  }
+  return kOk;
+}
+
 int fhe_keyswitch(const fhe_ctx* c, uint64_t* ks0, uint64_t* ks1, const uint64_t* d2,
                   const uint64_t* evk_b, const uint64_t* evk_a, uint32_t batch, void* ws,
                   fhe_stream_t s) {
   int rc = check_window(c, 0, c ? c->L : 0, c ? c->L : 0, "fhe_keyswitch");
   if (rc) return rc;
+  return fhe_keyswitch_level(c, ks0, ks1, d2, evk_b, evk_a, c->L, batch, ws, s);
+}
+
+int fhe_keyswitch_level(const fhe_ctx* c, uint64_t* ks0, uint64_t* ks1, const uint64_t* d2,
+                        const uint64_t* evk_b, const uint64_t* evk_a, uint32_t level,
+                        uint32_t batch, void* ws, fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_keyswitch_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_keyswitch_level"))) return rc;
   if (batch == 0) return kOk;
-  const uint64_t ct_words = (uint64_t)c->L * c->n;
+  const uint64_t ct_words = (uint64_t)level * c->n;
   // the whole batch at once: a pass must not overwrite a later pass's d2 (per-pass checks in the
   // launcher would miss an output shifted onto the next pass's input)
   if ((rc = ks_check_alias(ks0, ks1, d2, batch * ct_words, batch * ct_words, true,
                            "fhe_keyswitch")))
     return rc;
   const uint32_t pass = ks_pass_batch(c, batch);  // Infinity-Cache-sized passes
-  const size_t bytes = keyswitch_workspace_bytes(c, c->L, pass);
+  // the level's own regions: never more than fhe_keyswitch_workspace(ctx, L, pass)
+  const size_t bytes = keyswitch_workspace_bytes(c, level, pass, level);
   if ((rc = ensure_ws(c, bytes, &ws, hs(s)))) return rc;
   // c_all = INTT(d2) of one pass lives at the tail of the workspace (out of place: no copy of d2)
   const size_t call = (size_t)pass * ct_words * sizeof(uint64_t);
   uint64_t* c_all = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + bytes - call);
   // a prepared input when the fused ModUp applies: the INTT folds (D^_k)^-1 into its last stage
   const bool prep = ks_prepared(c);
-  CAll src = CAll::contiguous(c_all, c->L, c->n);
+  CAll src = CAll::contiguous(c_all, level, c->n);
   src.scaled = prep;
   for (uint32_t b0 = 0; b0 < batch; b0 += pass) {
     const uint32_t bn = std::min(pass, batch - b0);
     const uint64_t off = (uint64_t)b0 * ct_words;
-    if ((rc = launch_ntt_strided(c, false, d2 + off, ct_words, c_all, ct_words, bn, 0, c->L, hs(s),
-                                 prep ? c->d_nfold_up : nullptr, prep && ks_split30(c))))
+    if ((rc = launch_ntt_strided(c, false, d2 + off, ct_words, c_all, ct_words, bn, 0, level, hs(s),
+                                 prep ? ks_level_nfold_up(c, level) : nullptr,
+                                 prep && ks_split30(c))))
       return rc;
-    if ((rc = launch_keyswitch_shard(c, ks0 + off, ks1 + off, src, d2 + off, evk_b, evk_a, 0, c->L,
-                                     bn, ws, hs(s))))
+    if ((rc = launch_keyswitch_shard(c, ks0 + off, ks1 + off, src, d2 + off, evk_b, evk_a, 0, level,
+                                     bn, ws, hs(s), nullptr, nullptr, level)))
       return rc;
   }
   return kOk;
@@ -363,15 +382,23 @@ int fhe_rotate(const fhe_ctx* c, uint64_t* out, const uint64_t* in, uint32_t gal
                fhe_stream_t s) {
   int rc = check_window(c, 0, c ? c->L : 0, c ? c->L : 0, "fhe_rotate");
   if (rc) return rc;
+  return fhe_rotate_level(c, out, in, galois_elt, rot_b, rot_a, c->L, batch, ws, s);
+}
+
+int fhe_rotate_level(const fhe_ctx* c, uint64_t* out, const uint64_t* in, uint32_t galois_elt,
+                     const uint64_t* rot_b, const uint64_t* rot_a, uint32_t level, uint32_t batch,
+                     void* ws, fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_rotate_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_rotate_level"))) return rc;
   // the finish reads c0 through sigma (any word of its row block) while other workgroups write
-  // out: any overlap of the two [batch][2][L][N] spans races, not just out == in
-  const uint64_t span = (uint64_t)batch * 2 * c->L * c->n;
+  // out: any overlap of the two [batch][2][level][N] spans races, not just out == in
+  const uint64_t span = (uint64_t)batch * 2 * level * c->n;
   if (spans_overlap(out, span, in, span)) {
     set_error("fhe_rotate: out must not overlap in");
     return kInvalid;
   }
   if ((rc = ensure_ws(c, rotate_workspace_bytes(c, ks_pass_batch(c, batch)), &ws, hs(s)))) return rc;
-  return launch_rotate(c, out, in, galois_elt, rot_b, rot_a, batch, ws, hs(s));
+  return launch_rotate(c, out, in, galois_elt, rot_b, rot_a, level, batch, ws, hs(s));
 }
 
 size_t fhe_rotate_hoisted_workspace(const fhe_ctx* c, uint32_t batch) {
@@ -527,8 +554,20 @@ int fhe_mul_relin(const fhe_ctx* c, uint64_t* out, const uint64_t* a, const uint
                   void* ws, fhe_stream_t s) {
   int rc = check_window(c, 0, c ? c->L : 0, c ? c->L : 0, "fhe_mul_relin");
   if (rc) return rc;
+  return fhe_mul_relin_level(c, out, a, b, evk_b, evk_a, c->L, batch, rescale, ws, s);
+}
+
+int fhe_mul_relin_level(const fhe_ctx* c, uint64_t* out, const uint64_t* a, const uint64_t* b,
+                        const uint64_t* evk_b, const uint64_t* evk_a, uint32_t level,
+                        uint32_t batch, int rescale, void* ws, fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_mul_relin_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_mul_relin_level"))) return rc;
+  if (rescale && level < 2) {
+    set_error("fhe_mul_relin_level: rescale needs level >= 2");
+    return kInvalid;
+  }
   if ((rc = ensure_ws(c, mul_relin_workspace_bytes(c, ks_pass_batch(c, batch)), &ws, hs(s)))) return rc;
-  return launch_mul_relin(c, out, a, b, evk_b, evk_a, batch, rescale != 0, ws, hs(s));
+  return launch_mul_relin(c, out, a, b, evk_b, evk_a, level, batch, rescale != 0, ws, hs(s));
 }
 
 }  // extern "C"

@@ -129,7 +129,9 @@ int ctx_destroy(fhe_ctx* c) {
                     (void*)c->d_moddown_hat, (void*)c->d_modup_hat_w, (void*)c->d_modup_hat_rw,
                     (void*)c->d_moddown_hat_w, (void*)c->d_modup_hat_rwp,
                     (void*)c->d_moddown_hat_wp, (void*)c->d_rpinv, (void*)c->d_pinv, (void*)c->d_rs_tab,
-                    (void*)c->d_rs_half, c->workspace})
+                    (void*)c->d_rs_half, (void*)c->d_lvl_inv, (void*)c->d_lvl_hat,
+                    (void*)c->d_lvl_hat_w, (void*)c->d_lvl_hat_rw, (void*)c->d_lvl_hat_rwp,
+                    (void*)c->d_lvl_nfold_up, c->workspace})
     if (ptr) (void)hipFree(ptr);
   delete c;
   return kOk;

@@ -373,20 +373,26 @@ size_t rotate_workspace_bytes(const fhe_ctx* c, u32 batch) {
   return 2 * (size_t)batch * c->L * c->n * sizeof(u64) + keyswitch_workspace_bytes(c, c->L, batch);
 }
 
+// `level` Q-limbs (1 .. c->L) in in / out: the workspace regions are laid out for that many
+// (rotate_workspace_bytes, sized for c->L, covers every level).
 int launch_rotate(const fhe_ctx* c, u64* out, const u64* in, u32 galois_elt, const u64* rot_b,
-                  const u64* rot_a, u32 batch, void* ws, hipStream_t s) {
+                  const u64* rot_a, u32 level, u32 batch, void* ws, hipStream_t s) {
   if (c->K == 0) {
     set_error("rotate: context has no special primes (K = 0)");
     return kInvalid;
   }
+  if (level == 0 || level > c->L) {
+    set_error("rotate: level must be in [1, L]");
+    return kInvalid;
+  }
   if (batch == 0) return kOk;
-  const u32 L = c->L;
+  const u32 L = level;  // the live Q-limbs
   const u64 n = c->n, ln = (u64)L * n;
   // Infinity-Cache-sized passes (ks_pass_batch), each in the front of the workspace
   if (const u32 pass = ks_pass_batch(c, batch); pass < batch) {
     for (u32 b0 = 0; b0 < batch; b0 += pass) {
       if (int rc = launch_rotate(c, out + b0 * 2 * ln, in + b0 * 2 * ln, galois_elt, rot_b, rot_a,
-                                 std::min(pass, batch - b0), ws, s))
+                                 level, std::min(pass, batch - b0), ws, s))
         return rc;
     }
     return kOk;
@@ -402,11 +408,12 @@ int launch_rotate(const fhe_ctx* c, u64* out, const u64* in, u32 galois_elt, con
       (rc = launch_automorphism(c, sc1, ln, in + ln, 2 * ln, batch, 0, L, galois_elt, true, s)))
     return rc;
   // key-switch sigma(c1): its coefficient form goes to the tail of the key-switch workspace
-  const size_t kbytes = keyswitch_workspace_bytes(c, L, batch);
+  const size_t kbytes = keyswitch_workspace_bytes(c, L, batch, level);
   u64* c_all = reinterpret_cast<u64*>(reinterpret_cast<char*>(kws) + kbytes) - batch * ln;
   const bool prep = ks_prepared(c);  // the INTT emits ModUp's scaled inputs
   if ((rc = launch_ntt_strided(c, false, sc1, ln, c_all, ln, batch, 0, L, s,
-                               prep ? c->d_nfold_up : nullptr, prep && ks_split30(c))))
+                               prep ? ks_level_nfold_up(c, level) : nullptr,
+                               prep && ks_split30(c))))
     return rc;
   CAll call = CAll::contiguous(c_all, L, n);
   call.scaled = prep;
@@ -417,7 +424,7 @@ int launch_rotate(const fhe_ctx* c, u64* out, const u64* in, u32 galois_elt, con
   ep.add_bs = gather0 ? 2 * ln : ln;
   ep.add_gal = gather0 ? galois_elt : 0;
   return launch_keyswitch_shard(c, out, out + ln, call, sc1, rot_b, rot_a, 0, L, batch, kws, s,
-                                &ep);
+                                &ep, nullptr, level);
 }
 
 size_t rotate_hoisted_workspace_bytes(const fhe_ctx* c, u32 batch) {

@@ -106,6 +106,18 @@ struct fhe_ctx {
   // fold table for the INTT of d2 ahead of a key-switch (entries of limbs 0..L-1): N^-1 (D^_k)^-1
   // and psi^-N/2 N^-1 (D^_k)^-1 of limb k's digit, so the INTT emits ModUp's scaled inputs
   ulonglong2* d_nfold_up = nullptr;     // [L + K][4]
+  // Level tables (rns.hip build_rns_tables): a key-switch over the first l < L Q-limbs keeps the
+  // top-level digit width alpha, so its last digit [j alpha, l) is partial when l mod alpha != 0
+  // and that one digit's D^_k differ from the top level's.  Entry l of each table (l in [1, L),
+  // filled for every l, read only for the partial ones) holds the constants of level l's last
+  // digit in the layout of one digit of the table it stands in for.
+  ulonglong2* d_lvl_inv = nullptr;      // [L][alpha]
+  ulonglong2* d_lvl_hat = nullptr;      // [L][alpha][L + K]
+  ulonglong2* d_lvl_hat_w = nullptr;    // [L][alpha][L + K]
+  ulonglong2* d_lvl_hat_rw = nullptr;   // [L][alpha][L + K]
+  ulonglong2* d_lvl_hat_rwp = nullptr;  // [L][alpha][L + K]
+  // d_nfold_up per level: the entries of the last digit's limbs take that digit's (D^_k)^-1
+  ulonglong2* d_lvl_nfold_up = nullptr;  // [L][L + K][4]
 
   void* workspace = nullptr;
   size_t workspace_bytes = 0;
@@ -147,7 +159,8 @@ int launch_ntt_row_fwd_r2(const fhe_ctx* c, const u64* src, u64 spstride, u64* d
                           u32 polys, u32 limb0, u32 nlimbs, hipStream_t s);
 // Fused key-switch row kernel (ntt.hip, k_ks_row_inner): row-forward NTT of every ModUp digit's
 // column-passed rows + inner product with the key.  ext [dnum][batch][rows][N] (digit stride
-// ext_ds words), d2_own [batch][nq][N] NTT form, evk [dnum][rows][N], acc [2][batch][rows][N]
+// ext_ds words), d2_own [batch][nq][N] NTT form, evk [dnum][rows][N] (or the rows of a larger key,
+// KsRowArgs::key_rows), acc [2][batch][rows][N]
 // (second half at acc + acc_ws); row r -> limb r < nq ? base0 + r : base1 + r - nq.
 struct KsRowArgs {
   u64* acc;
@@ -170,6 +183,12 @@ struct KsRowArgs {
   const ulonglong2* rscale = nullptr;
   // the rows this launch covers: [row0, row0 + nrows) (nrows 0: all rows)
   u32 row0 = 0, nrows = 0;
+  // live digits (0: c->dnum): a level below the top has ceil(level / alpha) of them
+  u32 dnum = 0;
+  // rows of one digit of the key (0: `rows`, the key holds exactly this call's rows): digit stride
+  // key_rows N, and row r reads key row r < nq ? r : key_rows - (rows - nq) + (r - nq).  A level
+  // call reads the top-level key [dnum][L + K][N] in place: key_rows = L + K.
+  u32 key_rows = 0;
 };
 int launch_ks_row_inner(const fhe_ctx* c, const KsRowArgs& a, hipStream_t s);
 // ModUp column pass (ntt.hip, k_modup_col): converts a digit's S pre-scaled source rows
@@ -218,6 +237,7 @@ struct KsFinArgs {
   u64* ks0;
   u64* ks1;
   KsEpilogue ep;  // out_bs resolved
+  u32 dnum = 0, key_rows = 0;  // as KsRowArgs
 };
 int launch_ks_row_fin(const fhe_ctx* c, const KsFinArgs& a, hipStream_t s);
 // Hoisted rotations (galois.hip launch_rotate_hoisted): modup_only runs ModUp alone and leaves the
@@ -326,8 +346,25 @@ inline uint32_t ks_pass_batch(const fhe_ctx* c, uint32_t batch) {
 int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& call,
                            const u64* d2_own, const u64* evk_b, const u64* evk_a, u32 limb0,
                            u32 nlimbs, u32 batch, void* ws, hipStream_t s,
-                           const KsEpilogue* ep = nullptr, const KsHoist* hoist = nullptr);
-size_t keyswitch_workspace_bytes(const fhe_ctx* c, u32 nlimbs, u32 batch);
+                           const KsEpilogue* ep = nullptr, const KsHoist* hoist = nullptr,
+                           u32 level = 0);
+// level != 0 (then limb0 = 0, nlimbs = level, no hoist): the key-switch over the first `level`
+// Q-limbs with the top-level digit width and the top-level key [dnum][L + K][N] read in place
+// (key rows {0 .. level-1} u {L .. L+K-1} of the digits j < ks_level_digits); call holds `level`
+// limbs, prepared with ks_level_nfold_up's table.  level == L is the top-level call itself.
+inline u32 ks_level_digits(const fhe_ctx* c, u32 level) {
+  return (level + c->alpha - 1) / c->alpha;
+}
+// whether level's last digit is partial (its constants come from the d_lvl_* tables)
+inline bool ks_level_partial(const fhe_ctx* c, u32 level) {
+  return level < c->L && level % c->alpha != 0;
+}
+inline const ulonglong2* ks_level_nfold_up(const fhe_ctx* c, u32 level) {
+  return ks_level_partial(c, level) ? c->d_lvl_nfold_up + (size_t)level * 4 * (c->L + c->K)
+                                    : c->d_nfold_up;
+}
+// (level != 0: the regions of a level call, never more than the top level's)
+size_t keyswitch_workspace_bytes(const fhe_ctx* c, u32 nlimbs, u32 batch, u32 level = 0);
 // The key-switch aliasing rule (include/fhecore.h): each output span (out_words from ks0 / ks1)
 // either is d2 itself (same start, the contiguous layout: `contiguous`, out_words == d2_words) or
 // does not overlap d2's d2_words; with contiguous outputs ks0 and ks1 must not overlap each other
@@ -369,8 +406,9 @@ int launch_rescale(const fhe_ctx* c, u64* out, const u64* in, u32 polys, u32 nl,
                    void* ws, hipStream_t s);
 size_t rescale_workspace_bytes(const fhe_ctx* c, u32 polys, u32 nl);
 // in/out [batch][2][L][N] NTT form; rot_b/rot_a [dnum][L + K][N] (key for sigma_k(s) -> s)
+// (level: the Q-limbs of in / out, 1 .. L; the keys stay the top-level ones)
 int launch_rotate(const fhe_ctx* c, u64* out, const u64* in, u32 galois_elt, const u64* rot_b,
-                  const u64* rot_a, u32 batch, void* ws, hipStream_t s);
+                  const u64* rot_a, u32 level, u32 batch, void* ws, hipStream_t s);
 size_t rotate_workspace_bytes(const fhe_ctx* c, u32 batch);
 // `count` rotations of the same ciphertexts sharing one ModUp: out [count][batch][2][L][N],
 // galois[r] with its key rot_b[r] / rot_a[r] (host arrays of device pointers)
@@ -401,8 +439,10 @@ int launch_linear_transform(const fhe_ctx* c, u64* out, const u64* in, u32 n1, u
 size_t linear_transform_workspace_bytes(const fhe_ctx* c, u32 n2, u32 batch);
 
 // ---- launchers (pipeline.hip): SURVEY.md §8(f) row 4 -----------------------------------
+// (level: the Q-limbs of a / b, 1 .. L; the key stays the top-level one)
 int launch_mul_relin(const fhe_ctx* c, u64* out, const u64* a, const u64* b, const u64* evk_b,
-                     const u64* evk_a, u32 batch, bool rescale, void* ws, hipStream_t s);
+                     const u64* evk_a, u32 level, u32 batch, bool rescale, void* ws,
+                     hipStream_t s);
 size_t mul_relin_workspace_bytes(const fhe_ctx* c, u32 batch);
 
 // caller workspace, else the context's internal one grown to `bytes` (capi.cpp); an error while

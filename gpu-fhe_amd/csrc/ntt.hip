@@ -1508,7 +1508,9 @@ __global__ FHE_KATTR void k_moddown_row(const u64* __restrict__ conv, u64* __res
 //     final reduction (the products are accumulated as 128-bit integers, any 64-bit operand);
 // all digits publish to LDS slot j; then every thread combines 4 of its 16 positions for both
 // outputs: acc{0,1} = sum_j x_j * evk{b,a}[j][r] (128-bit sums of DNUM products, one reduce128).
-// Rows: r < nq -> own Q-limb base0 + r, else special limb base1 + (r - nq).
+// Rows: r < nq -> own Q-limb base0 + r, else special limb base1 + (r - nq).  Key: digit d's row r at
+// evk + d kds + (r < nq ? r : kprow + (r - nq)) N, so the same kernel reads a key holding exactly
+// these rows (kds = rows N, kprow = nq) or the rows of a level call inside the top-level key.
 // MONT (lz16 only): the ext rows arrive times R = 2^64 (k_modup_col with d_modup_hat_rw), the own
 // digit's d2 rows are taken times R here (by its otherwise idle wave), and each output is one
 // subtractive REDC of the 128-bit sum (R^-1 cancels the factor) plus one subtraction, instead of
@@ -1525,6 +1527,7 @@ __global__ FHE_KATTR void k_ks_row_inner(u64* __restrict__ acc, u64 acc_ws,
                                          const u64* __restrict__ evk_a, u32 rows, u32 nq,
                                          u32 row0, u32 nrows,
                                          u32 base0, u32 base1, u32 alpha, u32 L, u32 batch,
+                                         u64 kds, u32 kprow,
                                          u32 pinv, const ulonglong2* __restrict__ rscale,
                                          const ulonglong2* __restrict__ twf,
                                          const ulonglong2* __restrict__ twi,
@@ -1627,15 +1630,23 @@ __global__ FHE_KATTR void k_ks_row_inner(u64* __restrict__ acc, u64 acc_ws,
   static_assert(CW == 4 || CW == 2 || CW == 8, "combine width");
   const u32 cpos0 = threadIdx.x * CW;
   const u32 crow = cpos0 / G::R2, cpos = cpos0 % G::R2;
-  const u64 okey = (u64)r * N + (u64)(tile * H::ROWS + crow) * G::R2 + cpos;
+  const u64 opos = (u64)(tile * H::ROWS + crow) * G::R2 + cpos;  // position within the poly
+  const u64 okey = (u64)r * N + opos;
+  // the key: digit stride kds words, row r at key row r (Q rows) or kprow + (r - nq) (special
+  // rows); rows N and nq when the key holds exactly this call's rows, (L + K) N and L when a
+  // level call reads the top-level key in place (workgroup-uniform either way)
+  // (r + (kprow - nq) [r >= nq] in min / max arithmetic: as a compare-and-select on r the scalar
+  // value fails hipcc's instruction selection for gfx950, "illegal VGPR to SGPR copy")
+  const u32 krow = r + (kprow - nq) * min(1u, max(r + 1, nq) - nq);
+  const u64 kkey = (u64)krow * N + opos;
   const u64* lrow = lds + crow * H::ROWW;
   u64x2_t kbv[CW / 2][DNUM], kav[CW / 2][DNUM];
 #pragma unroll
   for (int e = 0; e < CW; e += 2) {
 #pragma unroll
     for (int d = 0; d < DNUM; ++d) {
-      kbv[e / 2][d] = *(const __attribute__((address_space(1))) u64x2_t*)(evk_b + (u64)d * rn + okey + e);
-      kav[e / 2][d] = *(const __attribute__((address_space(1))) u64x2_t*)(evk_a + (u64)d * rn + okey + e);
+      kbv[e / 2][d] = *(const __attribute__((address_space(1))) u64x2_t*)(evk_b + (u64)d * kds + kkey + e);
+      kav[e / 2][d] = *(const __attribute__((address_space(1))) u64x2_t*)(evk_a + (u64)d * kds + kkey + e);
     }
   }
   __syncthreads();
@@ -1750,7 +1761,7 @@ __global__ FHE_KATTR void k_ks_row_fin(const u64* __restrict__ ext, u64 ext_ds,
                                        const u64* __restrict__ d2_own,
                                        const u64* __restrict__ evk_b,
                                        const u64* __restrict__ evk_a, u32 rows, u32 nq,
-                                       u32 base0, u32 alpha, u32 L, u32 batch,
+                                       u32 base0, u32 alpha, u32 L, u32 batch, u64 kds,
                                        const ulonglong2* __restrict__ rscale,
                                        const u64* __restrict__ conv, u64* __restrict__ ks0,
                                        u64* __restrict__ ks1, KsEpilogue ep,
@@ -1837,15 +1848,15 @@ __global__ FHE_KATTR void k_ks_row_fin(const u64* __restrict__ ext, u64 ext_ds,
   const u32 cpos0 = threadIdx.x * CW;
   const u32 crow = cpos0 / G::R2, cpos = cpos0 % G::R2;
   const u64 orow = (u64)(tile * H::ROWS + crow) * G::R2 + cpos;  // position within the poly
-  const u64 okey = (u64)r * N + orow;
+  const u64 okey = (u64)r * N + orow;  // every row here is a Q row: key row r, digit stride kds
   u64* lrow = lds + crow * H::ROWW;
   u64x2_t kbv[CW / 2][DNUM], kav[CW / 2][DNUM], dv[CW / 2];
 #pragma unroll
   for (int e = 0; e < CW; e += 2) {
 #pragma unroll
     for (int d = 0; d < DNUM; ++d) {
-      kbv[e / 2][d] = *(const __attribute__((address_space(1))) u64x2_t*)(evk_b + (u64)d * rn + okey + e);
-      kav[e / 2][d] = *(const __attribute__((address_space(1))) u64x2_t*)(evk_a + (u64)d * rn + okey + e);
+      kbv[e / 2][d] = *(const __attribute__((address_space(1))) u64x2_t*)(evk_b + (u64)d * kds + okey + e);
+      kav[e / 2][d] = *(const __attribute__((address_space(1))) u64x2_t*)(evk_a + (u64)d * kds + okey + e);
     }
     dv[e / 2] = *(const __attribute__((address_space(1))) u64x2_t*)(d2_own + ((u64)b * nq + r) * N + orow + e);
   }
@@ -2172,18 +2183,23 @@ int ks_row_inner_dispatch(const fhe_ctx* c, const KsRowArgs& a, hipStream_t s) {
   const u32 nrows = a.nrows ? a.nrows : a.rows;
   if (int rc = check_grid((u64)nrows * a.batch * H::TILES, H::THR, 1, 1, "ks_row_inner")) return rc;
   const dim3 g((u32)((u64)nrows * a.batch * H::TILES));
-  switch (c->dnum) {
+  const u32 krows = a.key_rows ? a.key_rows : a.rows;
+  const u64 kds = (u64)krows * (1ull << LOGN);
+  const u32 kprow = krows - (a.rows - a.nq);
+  switch (a.dnum ? a.dnum : c->dnum) {
 #define D(k)                                                                                    \
   case k:                                                                                       \
     if (HD == 16 && a.mont)                                                                     \
       k_ks_row_inner<LOGN, HD, k, HD == 16><<<g, H::THR, 0, s>>>(                               \
           a.acc, a.acc_ws, a.ext, a.ext_ds, a.d2_own, a.evk_b, a.evk_a, a.rows, a.nq, a.row0,   \
-          nrows, a.base0, a.base1, a.alpha, a.L, a.batch, a.pinv, a.rscale, c->d_tw_fwd,       \
+          nrows, a.base0, a.base1, a.alpha, a.L, a.batch, kds, kprow, a.pinv, a.rscale,        \
+          c->d_tw_fwd,                                                                          \
           c->d_tw_inv, c->d_mods);                                                              \
     else                                                                                        \
       k_ks_row_inner<LOGN, HD, k><<<g, H::THR, 0, s>>>(                                         \
           a.acc, a.acc_ws, a.ext, a.ext_ds, a.d2_own, a.evk_b, a.evk_a, a.rows, a.nq, a.row0,   \
-          nrows, a.base0, a.base1, a.alpha, a.L, a.batch, a.pinv, a.rscale, c->d_tw_fwd,       \
+          nrows, a.base0, a.base1, a.alpha, a.L, a.batch, kds, kprow, a.pinv, a.rscale,        \
+          c->d_tw_fwd,                                                                          \
           c->d_tw_inv, c->d_mods);                                                              \
     break;
     D(1) D(2) D(3) D(4)
@@ -2365,12 +2381,13 @@ int ks_row_fin_dispatch(const fhe_ctx* c, const KsFinArgs& a, hipStream_t s) {
   using H = HmGeo<LOGN>;
   if (int rc = check_grid((u64)a.nq * a.batch * H::TILES, H::THR, 1, 1, "ks_row_fin")) return rc;
   const dim3 g((u32)((u64)a.nq * a.batch * H::TILES));
-  switch (c->dnum) {
+  const u64 kds = (u64)(a.key_rows ? a.key_rows : a.rows) * (1ull << LOGN);
+  switch (a.dnum ? a.dnum : c->dnum) {
 #define D(k)                                                                                     \
   case k:                                                                                        \
     k_ks_row_fin<LOGN, k><<<g, H::THR, 0, s>>>(a.ext, a.ext_ds, a.d2_own, a.evk_b, a.evk_a,     \
                                                a.rows, a.nq, a.base0, a.alpha, a.L, a.batch,     \
-                                               a.rscale, a.conv, a.ks0, a.ks1, a.ep, c->d_tw_fwd, \
+                                               kds, a.rscale, a.conv, a.ks0, a.ks1, a.ep, c->d_tw_fwd, \
                                                c->d_mods);                                       \
     break;
     D(1) D(2) D(3) D(4)

@@ -63,25 +63,32 @@ size_t mul_relin_workspace_bytes(const fhe_ctx* c, u32 batch) {
          keyswitch_workspace_bytes(c, c->L, batch);
 }
 
+// `level` Q-limbs (1 .. c->L) in a, b and out: the workspace regions below are laid out for that
+// many, so mul_relin_workspace_bytes (sized for c->L) covers every level.
 int launch_mul_relin(const fhe_ctx* c, u64* out, const u64* a, const u64* b, const u64* evk_b,
-                     const u64* evk_a, u32 batch, bool rescale, void* ws, hipStream_t s) {
+                     const u64* evk_a, u32 level, u32 batch, bool rescale, void* ws,
+                     hipStream_t s) {
   if (c->K == 0) {
     set_error("mul_relin: context has no special primes (K = 0)");
     return kInvalid;
   }
-  if (rescale && c->L < 2) {
-    set_error("mul_relin: rescale needs L >= 2");
+  if (level == 0 || level > c->L) {
+    set_error("mul_relin: level must be in [1, L]");
+    return kInvalid;
+  }
+  if (rescale && level < 2) {
+    set_error("mul_relin: rescale needs at least 2 limbs");
     return kInvalid;
   }
   if (batch == 0) return kOk;
-  const u32 L = c->L;
+  const u32 L = level;  // the live Q-limbs
   const u64 n = c->n, ln = (u64)L * n;
   // Infinity-Cache-sized passes (ks_pass_batch), each in the front of the workspace
   if (const u32 pass = ks_pass_batch(c, batch); pass < batch) {
     const u64 out_bs = 2 * (u64)(rescale ? L - 1 : L) * n;
     for (u32 b0 = 0; b0 < batch; b0 += pass) {
       if (int rc = launch_mul_relin(c, out + b0 * out_bs, a + b0 * 2 * ln, b + b0 * 2 * ln, evk_b,
-                                    evk_a, std::min(pass, batch - b0), rescale, ws, s))
+                                    evk_a, level, std::min(pass, batch - b0), rescale, ws, s))
         return rc;
     }
     return kOk;
@@ -100,12 +107,13 @@ int launch_mul_relin(const fhe_ctx* c, u64* out, const u64* a, const u64* b, con
   prof_mark(s, "tensor_ntt");
   // d2 = d[b][2]: gather to a contiguous [batch][L][N] operand for the key-switch (its INTT lands
   // at the tail of the key-switch workspace, as in fhe_keyswitch)
-  const size_t kbytes = keyswitch_workspace_bytes(c, L, batch);
+  const size_t kbytes = keyswitch_workspace_bytes(c, L, batch, level);
   u64* c_all = reinterpret_cast<u64*>(reinterpret_cast<char*>(kws) + kbytes) - batch * ln;
   int rc;
   const bool prep = ks_prepared(c);  // the INTT emits ModUp's scaled inputs
   if ((rc = launch_ntt_strided(c, false, d2, ln, c_all, ln, batch, 0, L, s,
-                               prep ? c->d_nfold_up : nullptr, prep && ks_split30(c))))
+                               prep ? ks_level_nfold_up(c, level) : nullptr,
+                               prep && ks_split30(c))))
     return rc;
   CAll call = CAll::contiguous(c_all, L, n);
   call.scaled = prep;
@@ -118,7 +126,7 @@ int launch_mul_relin(const fhe_ctx* c, u64* out, const u64* a, const u64* b, con
   ep.add1 = d + ln;
   ep.add_bs = 2 * ln;
   if ((rc = launch_keyswitch_shard(c, dst, dst + ln, call, d2, evk_b, evk_a, 0, L, batch, kws, s,
-                                   &ep)))
+                                   &ep, nullptr, level)))
     return rc;
   prof_mark(s, "relin_keyswitch");
   if (rescale) {

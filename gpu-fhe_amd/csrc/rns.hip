@@ -122,7 +122,9 @@ __global__ __launch_bounds__(kThreads) void k_baseconv(const u64* __restrict__ i
 // coefficients, y = row r (limb and modulus uniform per workgroup).  Each thread holds its
 // 2 DNUM evaluation-key words in registers and walks the batch, so the key -- the dominant
 // traffic of a key-switch -- is read once per batch; the DNUM products of a sum are accumulated
-// as 128-bit integers (< 16 q^2) and reduced once (reduce128).
+// as 128-bit integers (< 16 q^2) and reduced once (reduce128).  The key's digit stride is kds words
+// and row r's key row r < nq ? r : kprow + (r - nq): rows N and nq for a key holding exactly these
+// rows, (L + K) N and L when a level call reads the top-level key in place.
 constexpr int kMaxDnum = 16;
 template <int DNUM>
 __global__ __launch_bounds__(kThreads) void k_ks_inner(u64* __restrict__ acc, u64 acc_ws,
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void k_ks_inner(u64* __restrict__ acc, u6
                                                        u32 nq, RowMap map, u32 alpha, u32 L,
                                                        u32 batch, u32 log_n,
                                                        const ModParams* __restrict__ mods,
-                                                       u32 gal) {
+                                                       u32 gal, u64 kds, u32 kprow) {
   const u32 r = blockIdx.y;
   const u64 n = 1ull << log_n, rn = (u64)rows * n;
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -147,14 +149,16 @@ __global__ __launch_bounds__(kThreads) void k_ks_inner(u64* __restrict__ acc, u6
     si = __builtin_bitreverse32((g - 1) >> 1) >> sh;
   }
   const u64 es = (u64)r * n + si;
+  // the key's digit stride and this row's key row (a level call reads the top-level key in place)
+  const u64 ke = (u64)(r < nq ? r : kprow + (r - nq)) * n + i;
   const u32 limb = map.limb(r);
   const ModParams m = mods[limb];
   const u32 own = limb < L ? limb / alpha : 0xffffffffu;
   u64 kb[DNUM], ka[DNUM];
 #pragma unroll
   for (int j = 0; j < DNUM; ++j) {
-    kb[j] = evk_b[(u64)j * rn + e];
-    ka[j] = evk_a[(u64)j * rn + e];
+    kb[j] = evk_b[(u64)j * kds + ke];
+    ka[j] = evk_a[(u64)j * kds + ke];
   }
   if (m.mu == 0) {  // wide modulus (uniform): DNUM products could pass 2^128, reduce each
     for (u32 b = 0; b < batch; ++b) {
@@ -393,15 +397,48 @@ int build_rns_tables(fhe_ctx* c) {
       (rc = upload(&c->d_pinv, pinv)) || (rc = upload(&c->d_nfold_down, nf_down)) ||
       (rc = upload(&c->d_nfold_up, nf_up)))
     return rc;
+  // Level tables: level l keeps the digit width alpha, so its last digit is [lo, l) with
+  // lo = alpha (ceil(l / alpha) - 1); where that digit is partial its D^_k (hence every table
+  // derived from them) differ from the top level's.  Entry l is filled for every l in [1, L) (a
+  // full digit reproduces the top-level constants) and read only for the partial ones.
+  std::vector<Pair64> lv_inv((size_t)L * alpha, Pair64{0, 0}),
+      lv_hat((size_t)L * alpha * M, Pair64{0, 0}), lv_nf((size_t)L * 4 * M, Pair64{0, 0});
+  for (u32 l = 1; l < L; ++l) {
+    const u32 lo = (l - 1) / alpha * alpha;
+    std::vector<Pair64> inv, hat;
+    conv_tables(c->moduli, lo, l - lo, inv, hat);
+    std::copy(inv.begin(), inv.end(), lv_inv.begin() + (size_t)l * alpha);
+    std::copy(hat.begin(), hat.end(), lv_hat.begin() + (size_t)l * alpha * M);
+    std::copy(nf_up.begin(), nf_up.end(), lv_nf.begin() + (size_t)l * 4 * M);
+    for (u32 k = lo; k < l; ++k) {
+      const u64 q = c->moduli[k];
+      const u64 s = mulmod_u64(powmod_u64(c->n % q, q - 2, q), inv[k - lo].x, q);
+      const u64 w = powmod_u64(powmod_u64(c->psi[k], q - 2, q), c->n / 2, q);  // psi^-N/2
+      lv_nf[((size_t)l * M + k) * 4] = shoup_pair(s, q);
+      lv_nf[((size_t)l * M + k) * 4 + 1] = shoup_pair(mulmod_u64(w, s, q), q);
+    }
+  }
+  std::vector<Pair64> lv_hat_r(lv_hat);
+  for (size_t i = 0; i < lv_hat.size(); ++i) {
+    const u64 t = c->moduli[i % M];
+    lv_hat_r[i].y = (u64)(((u128)lv_hat[i].y << 64) % t);
+  }
+  if ((rc = upload(&c->d_lvl_inv, lv_inv)) || (rc = upload(&c->d_lvl_hat, lv_hat)) ||
+      (rc = upload(&c->d_lvl_hat_w, with_w0(lv_hat, false))) ||
+      (rc = upload(&c->d_lvl_hat_rw, with_w0(lv_hat_r, false))) ||
+      (rc = upload(&c->d_lvl_hat_rwp, with_w0(lv_hat_r, true))) ||
+      (rc = upload(&c->d_lvl_nfold_up, lv_nf)))
+    return rc;
   return kOk;
 }
 
-size_t keyswitch_workspace_bytes(const fhe_ctx* c, u32 nlimbs, u32 batch) {
+size_t keyswitch_workspace_bytes(const fhe_ctx* c, u32 nlimbs, u32 batch, u32 level) {
   const u64 rows = nlimbs + c->K;
   // ext [dnum][batch][rows][N] + acc [2][batch][rows][N] + conv [2][batch][nlimbs][N]
   // + y [batch][alpha][N] (fused ModUp) + c_all [batch][L][N] (single-device form, at the tail)
-  return (u64)batch * ((u64)c->dnum * rows + 2 * rows + 2 * nlimbs + c->alpha + c->L) * c->n *
-         sizeof(u64);
+  // (a level call: its live digits and its own limbs in place of dnum and L)
+  const u64 dl = level ? ks_level_digits(c, level) : c->dnum, cl = level ? level : c->L;
+  return (u64)batch * (dl * rows + 2 * rows + 2 * nlimbs + c->alpha + cl) * c->n * sizeof(u64);
 }
 
 int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const u64* c_all,
@@ -414,7 +451,11 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const u64* c_al
 int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& call,
                            const u64* d2_own, const u64* evk_b, const u64* evk_a, u32 limb0,
                            u32 nlimbs, u32 batch, void* ws, hipStream_t s,
-                           const KsEpilogue* epi, const KsHoist* hoist) {
+                           const KsEpilogue* epi, const KsHoist* hoist, u32 level) {
+  if (level && (level > c->L || limb0 != 0 || nlimbs != level || hoist)) {
+    set_error("keyswitch: a level call covers Q-limbs [0, level), level <= L, unhoisted");
+    return kInvalid;
+  }
   if (c->K == 0) {
     set_error("keyswitch: context has no special primes (K = 0)");
     return kInvalid;
@@ -442,9 +483,20 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
       return rc;
   }
   const u32 L = c->L, K = c->K, M = L + K, alpha = c->alpha, rows = nlimbs + K;
+  // The chain's live Q-limbs and digits: all L and dnum, or a level call's first `level` limbs in
+  // ceil(level / alpha) digits of the same width, the last one partial where alpha does not divide
+  // level (its constants: the d_lvl_* tables).  The key is the top-level one either way; a level
+  // call reads rows {0 .. level-1} u {L .. L+K-1} of its digits j < dl in place (key_rows).
+  const u32 Lq = level ? level : L, dl = level ? ks_level_digits(c, level) : c->dnum;
+  const u32 key_rows = level ? M : rows;
+  const bool part = level && ks_level_partial(c, level);
+  // digit j's slice of a [dnum][alpha](x [L + K]) table: the level's own for a partial last digit
+  auto dig = [&](const ulonglong2* top, const ulonglong2* lvl, u32 j, size_t per) {
+    return part && j == dl - 1 ? lvl + (size_t)level * per : top + (size_t)j * per;
+  };
   const u64 n = c->n, rn = (u64)rows * n, B = batch;
-  u64* ext = static_cast<u64*>(ws);          // [dnum][B][rows][N]
-  u64* acc = ext + (u64)c->dnum * B * rn;    // [2][B][rows][N]
+  u64* ext = static_cast<u64*>(ws);          // [dl][B][rows][N]
+  u64* acc = ext + (u64)dl * B * rn;         // [2][B][rows][N]
   u64* conv = acc + 2 * B * rn;              // [2][B][nlimbs][N]
   const u64 acc_ws = B * rn;
   const RowMap map{nlimbs, limb0, L};
@@ -477,7 +529,7 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
   // ModDown's finish: k_moddown_row after the fused conversion (fused_down; a hoisted rotation's
   // inner step too, with its own scratch for the INTT output) or after k_baseconv (fused), else
   // the unfused k_moddown_finish
-  const bool fused_down = K <= 4 && ((fused && (u64)c->dnum * rows >= 2 * (u64)K) ||
+  const bool fused_down = K <= 4 && ((fused && (u64)dl * rows >= 2 * (u64)K) ||
                                      (hoist && hoist->ydn && ks_hoist_fused_down(c)));
   // ModDown's P^-1 folded into the accumulators' Q rows (the ModUp conversion tables of the Q
   // targets and the own digit's R factor carry P^-1) and into the P -> Q conversion table, so
@@ -501,8 +553,8 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
   // per-digit scaling pass into the shared yws) put every digit's conversion pass in one launch.
   ModUpColArgs pend[4];
   u32 npend = 0;
-  for (u32 j = 0; j < c->dnum; ++j) {
-    const u32 lo = j * alpha, hi = std::min(L, lo + alpha);
+  for (u32 j = 0; j < dl; ++j) {
+    const u32 lo = j * alpha, hi = std::min(Lq, lo + alpha);
     u64* e = ext + (u64)j * B * rn;
     KOff ko{};  // the digit's source rows in c_all
     for (u32 k = 0; k < hi - lo; ++k) ko.o[k] = call.off(lo + k, n);
@@ -515,8 +567,8 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
       for (u32 k = 0; k < S; ++k) yoff[k] = ko.o[k];
       if (!call.scaled) {
         k_modup_scale<<<dim3((u32)(n / kThreads), S, batch), kThreads, 0, s>>>(
-            call.ptr, call.bs, ko, lo, yws, S, c->log_n, c->d_modup_inv + (size_t)j * alpha,
-            c->d_mods, ks_split30(c));
+            call.ptr, call.bs, ko, lo, yws, S, c->log_n,
+            dig(c->d_modup_inv, c->d_lvl_inv, j, alpha), c->d_mods, ks_split30(c));
         FHE_HIP_CHECK(hipGetLastError());
         ysrc = yws;
         ybs = (u64)S * n;
@@ -528,10 +580,9 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
       const u32 skip_at = skip_len ? own_lo - limb0 : rows;
       const ModUpColArgs ma{ysrc, ybs, {yoff[0], yoff[1], yoff[2], yoff[3]}, e, rn, S,
                             rows - skip_len, skip_at, skip_len, nlimbs, limb0, L, batch,
-                            (pscale     ? c->d_modup_hat_rwp
-                             : mont_ext ? c->d_modup_hat_rw
-                                        : c->d_modup_hat_w) +
-                                (size_t)j * alpha * M,
+                            pscale     ? dig(c->d_modup_hat_rwp, c->d_lvl_hat_rwp, j, alpha * M)
+                            : mont_ext ? dig(c->d_modup_hat_rw, c->d_lvl_hat_rw, j, alpha * M)
+                                       : dig(c->d_modup_hat_w, c->d_lvl_hat_w, j, alpha * M),
                             M};
       if (call.scaled && npend < 4) {
         pend[npend++] = ma;
@@ -541,8 +592,9 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
       continue;
     }
     const BcArgs up{call.ptr, call.bs, ko, lo, e, rn, rows, map, lo, hi, batch};
-    if ((rc = baseconv_any(hi - lo, up, n, c->d_modup_inv + (size_t)j * alpha,
-                           c->d_modup_hat + (size_t)j * alpha * M, M, c->d_mods, c->wide, s)))
+    if ((rc = baseconv_any(hi - lo, up, n, dig(c->d_modup_inv, c->d_lvl_inv, j, alpha),
+                           dig(c->d_modup_hat, c->d_lvl_hat, j, alpha * M), M, c->d_mods, c->wide,
+                           s)))
       return rc;
     // own Q-limbs outside [lo, hi): up to two ranges, then the P-limbs
     const u32 a0 = limb0, a1 = std::min(limb0 + nlimbs, lo);
@@ -583,6 +635,8 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
   if (fused) {
     KsRowArgs ka{acc, acc_ws, ext, B * rn, d2_own, evk_b, evk_a, rows, nlimbs, limb0, L,
                  alpha, L, batch, mont_ext};
+    ka.dnum = dl;
+    ka.key_rows = key_rows;
     ka.pinv = row_pinv ? 1u : 0u;
     ka.rscale = pscale ? c->d_rpinv : nullptr;
     if (qfin) {
@@ -592,11 +646,12 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
     if ((rc = launch_ks_row_inner(c, ka, s))) return rc;
   }
   const dim3 gi((u32)(n / kThreads), rows);
-  if (!fused && !(hoist && hoist->acc_ready)) switch (c->dnum) {
+  if (!fused && !(hoist && hoist->acc_ready)) switch (dl) {
 #define X(k)                                                                                     \
   case k:                                                                                        \
     k_ks_inner<k><<<gi, kThreads, 0, s>>>(acc, acc_ws, ext, d2_own, evk_b, evk_a, rows, nlimbs, \
-                                          map, alpha, L, batch, c->log_n, c->d_mods, gal);      \
+                                          map, alpha, L, batch, c->log_n, c->d_mods, gal,       \
+                                          (u64)key_rows * n, key_rows - K);                     \
     break;
     X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 #undef X
@@ -627,7 +682,7 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
     prof_mark(s, "ks_moddown_col");
     if (qfin) {
       const KsFinArgs fa{ext, B * rn, d2_own, evk_b, evk_a, rows, nlimbs, limb0, alpha, L, batch,
-                         c->d_rpinv, conv, ks0, ks1, ep};
+                         c->d_rpinv, conv, ks0, ks1, ep, dl, key_rows};
       if ((rc = launch_ks_row_fin(c, fa, s))) return rc;
       prof_mark(s, "ks_row_fin");
       return kOk;

@@ -48,6 +48,9 @@ SIGNATURES = {
     "fhe_keyswitch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "fhe_keyswitch_shard": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp,
                                    _vp]),
+    "fhe_keyswitch_level": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "fhe_mul_relin_level": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _i32, _vp, _vp]),
+    "fhe_rotate_level": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp]),
     "fhe_comm_get_unique_id": (_i32, [ctypes.c_char_p]),
     "fhe_comm_create": (_i32, [ctypes.POINTER(_vp), ctypes.c_char_p, _i32, _i32, _i32]),
     "fhe_comm_destroy": (_i32, [_vp]),

@@ -277,18 +277,27 @@ class Context:
                   "fhe_baseconv")
         return out
 
+    def _level(self, t, who):
+        """The level of t [..., l, N]: its number of Q-limbs l, 1 <= l <= L."""
+        lv = t.shape[-2]
+        if not 1 <= lv <= self.L:
+            raise ValueError(f"{who}: {lv} limbs, expected 1 .. L = {self.L}")
+        return lv
+
     def keyswitch(self, d2, evk_b, evk_a, workspace=None, out=None):
-        """d2 [L, N] or [batch, L, N] NTT form; evk_b/evk_a [dnum, L + K, N] NTT form (one key for the
-        whole batch) -> (ks0, ks1) shaped like d2, NTT form.
+        """d2 [l, N] or [batch, l, N] NTT form over the first l Q-limbs (1 <= l <= L: the level is
+        taken from the shape); evk_b/evk_a [dnum, L + K, N] NTT form, the top-level key at every
+        level (one key for the whole batch) -> (ks0, ks1) shaped like d2, NTT form.
         out = (ks0, ks1): caller-provided outputs shaped like d2 (either may be d2 itself, in place;
         any other overlap with d2 or between them raises FheError, fhecore.h)."""
         for t, nm in ((d2, "d2"), (evk_b, "evk_b"), (evk_a, "evk_a")):
             _check_tensor(t, nm, (self.n,))
         if tuple(evk_b.shape) != (self.dnum, self.L + self.K, self.n) or evk_a.shape != evk_b.shape:
             raise ValueError("keyswitch: evk must be [dnum, L + K, N]")
-        if d2.shape[-2] != self.L:
-            raise ValueError("keyswitch: d2 must be [..., L, N]")
-        batch = d2.numel() // (self.L * self.n)
+        if d2.dim() < 2:
+            raise ValueError("keyswitch: d2 must be [..., l, N]")
+        lv = self._level(d2, "keyswitch: d2")
+        batch = d2.numel() // (lv * self.n)
         if out is None:
             ks0, ks1 = _empty_like(d2), _empty_like(d2)
         else:
@@ -299,8 +308,13 @@ class Context:
             lib.fhe_keyswitch_workspace(self._ptr, self.L,
                                         lib.fhe_keyswitch_pass_batch(self._ptr, batch)))
         with torch.cuda.device(self.device):
-            check(lib.fhe_keyswitch(self._ptr, _ptr(ks0), _ptr(ks1), _ptr(d2), _ptr(evk_b),
-                                    _ptr(evk_a), batch, _ptr(ws), _stream(d2)), "fhe_keyswitch")
+            if lv == self.L:
+                check(lib.fhe_keyswitch(self._ptr, _ptr(ks0), _ptr(ks1), _ptr(d2), _ptr(evk_b),
+                                        _ptr(evk_a), batch, _ptr(ws), _stream(d2)), "fhe_keyswitch")
+            else:
+                check(lib.fhe_keyswitch_level(self._ptr, _ptr(ks0), _ptr(ks1), _ptr(d2),
+                                              _ptr(evk_b), _ptr(evk_a), lv, batch, _ptr(ws),
+                                              _stream(d2)), "fhe_keyswitch_level")
         return ks0, ks1
 
     # ---- rescale and rotation -------------------------------------
@@ -338,20 +352,30 @@ class Context:
         return out
 
     def rotate(self, ct, galois_elt: int, rot_b, rot_a, workspace=None, out=None):
-        """ct [..., 2, L, N] NTT form -> (sigma c0 + KS0(sigma c1), KS1(sigma c1)) with the
-        key-switch key rot_b/rot_a [dnum, L + K, N] from sigma_k(s) to s.  out: a caller-provided
-        output shaped like ct, which must not overlap ct (FheError otherwise, fhecore.h)."""
-        _check_tensor(ct, "ct", (2, self.L, self.n))
+        """ct [..., 2, l, N] NTT form (1 <= l <= L, the level taken from the shape) ->
+        (sigma c0 + KS0(sigma c1), KS1(sigma c1)) with the key-switch key rot_b/rot_a
+        [dnum, L + K, N] from sigma_k(s) to s, the top-level key at every level.  out: a
+        caller-provided output shaped like ct, which must not overlap ct (FheError otherwise,
+        fhecore.h)."""
+        _check_tensor(ct, "ct", (self.n,))
+        if ct.dim() < 3 or ct.shape[-3] != 2:
+            raise ValueError("rotate: ct must be [..., 2, l, N]")
+        lv = self._level(ct, "rotate: ct")
         if tuple(rot_b.shape) != (self.dnum, self.L + self.K, self.n) or rot_a.shape != rot_b.shape:
             raise ValueError("rotate: key must be [dnum, L + K, N]")
-        batch = ct.numel() // (2 * self.L * self.n)
+        batch = ct.numel() // (2 * lv * self.n)
         out = _empty_like(ct) if out is None else _check_out(out, ct, ct.shape, "rotate: out")
         lib = load()
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_rotate_workspace(self._ptr, lib.fhe_keyswitch_pass_batch(self._ptr, batch)))
         with torch.cuda.device(self.device):
-            check(lib.fhe_rotate(self._ptr, _ptr(out), _ptr(ct), galois_elt, _ptr(rot_b),
-                                 _ptr(rot_a), batch, _ptr(ws), _stream(ct)), "fhe_rotate")
+            if lv == self.L:
+                check(lib.fhe_rotate(self._ptr, _ptr(out), _ptr(ct), galois_elt, _ptr(rot_b),
+                                     _ptr(rot_a), batch, _ptr(ws), _stream(ct)), "fhe_rotate")
+            else:
+                check(lib.fhe_rotate_level(self._ptr, _ptr(out), _ptr(ct), galois_elt,
+                                           _ptr(rot_b), _ptr(rot_a), lv, batch, _ptr(ws),
+                                           _stream(ct)), "fhe_rotate_level")
         return out
 
     def rotate_hoisted(self, ct, galois_elts, rot_keys, workspace=None, out=None):
@@ -601,16 +625,18 @@ class Context:
 
     # ---- fused multiply -> relinearise -> rescale ------------------
     def mul_relin(self, a, b, evk_b, evk_a, rescale: bool = True, workspace=None, out=None):
-        """a, b [..., 2, L, N] NTT form -> Relin(a x b) [..., 2, L, N] (rescale: [..., 2, L-1, N]),
-        NTT form (oracle: pyoracle.mul_relin)."""
-        _check_tensor(a, "a", (2, self.L, self.n))
-        _check_tensor(b, "b", (2, self.L, self.n))
-        if a.shape != b.shape:
-            raise ValueError("mul_relin: a and b must have the same shape")
+        """a, b [..., 2, l, N] NTT form (1 <= l <= L, the level taken from the shape) ->
+        Relin(a x b) [..., 2, l, N] (rescale: [..., 2, l-1, N], needs l >= 2), NTT form; evk_b /
+        evk_a [dnum, L + K, N], the top-level key at every level (oracle: pyoracle.mul_relin)."""
+        _check_tensor(a, "a", (self.n,))
+        _check_tensor(b, "b", (self.n,))
+        if a.shape != b.shape or a.dim() < 3 or a.shape[-3] != 2:
+            raise ValueError("mul_relin: a and b must both be [..., 2, l, N]")
+        lv = self._level(a, "mul_relin: a")
         if tuple(evk_b.shape) != (self.dnum, self.L + self.K, self.n) or evk_a.shape != evk_b.shape:
             raise ValueError("mul_relin: key must be [dnum, L + K, N]")
-        batch = a.numel() // (2 * self.L * self.n)
-        shape = (*a.shape[:-2], self.L - (1 if rescale else 0), self.n)
+        batch = a.numel() // (2 * lv * self.n)
+        shape = (*a.shape[:-2], lv - (1 if rescale else 0), self.n)
         if out is None:
             out = _empty(shape, dtype=a.dtype, device=a.device)
         else:
@@ -619,9 +645,14 @@ class Context:
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_mul_relin_workspace(self._ptr, lib.fhe_keyswitch_pass_batch(self._ptr, batch)))
         with torch.cuda.device(self.device):
-            check(lib.fhe_mul_relin(self._ptr, _ptr(out), _ptr(a), _ptr(b), _ptr(evk_b),
-                                    _ptr(evk_a), batch, int(rescale), _ptr(ws), _stream(a)),
-                  "fhe_mul_relin")
+            if lv == self.L:
+                check(lib.fhe_mul_relin(self._ptr, _ptr(out), _ptr(a), _ptr(b), _ptr(evk_b),
+                                        _ptr(evk_a), batch, int(rescale), _ptr(ws), _stream(a)),
+                      "fhe_mul_relin")
+            else:
+                check(lib.fhe_mul_relin_level(self._ptr, _ptr(out), _ptr(a), _ptr(b), _ptr(evk_b),
+                                              _ptr(evk_a), lv, batch, int(rescale), _ptr(ws),
+                                              _stream(a)), "fhe_mul_relin_level")
         return out
 
     # ---- wire format ----------------------------------------------

@@ -59,7 +59,9 @@ int fhe_gen_moduli(uint32_t log_n, uint32_t count, uint32_t bits, uint32_t skip,
 /* ---- context ------------------------------------------------------------------------ */
 /* Creates a context on HIP device `device` for ring degree N = 2^log_n (10 <= log_n <= 17) with
  * Q-primes q[0..L) and special primes p[0..K) (K may be 0: no key-switch) and dnum gadget digits.
- * Every modulus must be a distinct prime < 2^61 with q = 1 (mod 2N).
+ * Every modulus must be a distinct prime < 2^63 with q = 1 (mod 2N).  Moduli below 2^61 take the
+ * lazy-range NTTs and, with dnum <= 4, the fused key-switch kernels; a context with any modulus in
+ * [2^61, 2^63) runs exact butterflies and the unfused key-switch (same results, slower).
  * Precomputes psi^brv twiddles (psi = g^((q-1)/2N), g the smallest primitive root), Shoup
  * companions, Barrett constants and key-switch base-conversion tables; uploads them.
  * Replaces: nothing in the reference (it passes MOD per call, arithmetic.py:3). */
@@ -161,6 +163,34 @@ int fhe_keyswitch_shard(const fhe_ctx* ctx, uint64_t* ks0, uint64_t* ks1, const 
                         const uint64_t* d2_own, const uint64_t* evk_b, const uint64_t* evk_a,
                         uint32_t limb0, uint32_t nlimbs, uint32_t batch, void* workspace,
                         fhe_stream_t stream);
+
+/* ---- levels below the top: key-switch, multiply-relinearise and rotation over l <= L limbs ----
+ * `level` = l is the number of live Q-limbs, 1 <= l <= L: ciphertexts are [batch][2][l][N], d2 /
+ * ks0 / ks1 [batch][l][N] (the rescaled product [batch][2][l-1][N]), NTT form.  The keys are the
+ * caller's top-level keys [dnum][L + K][N], read in place: the same key serves every level.  The
+ * level-l key-switch keeps the top-level digit width alpha = ceil(L / dnum): digits
+ * D_j = [j alpha, min(l, (j + 1) alpha)) for j < ceil(l / alpha), key rows {0 .. l-1} u
+ * {L .. L+K-1} of those digits (the last digit may be partial; its conversion constants are
+ * precomputed per level at context creation).  level == L is bit-identical to fhe_keyswitch /
+ * fhe_mul_relin / fhe_rotate, which are these calls with level = L.
+ * Errors: level == 0, level > L, or rescale with level < 2 return FHE_EINVAL before any launch;
+ * the aliasing rules are those of the top-level forms with l in place of L.
+ * Workspace: fhe_keyswitch_workspace(ctx, L, pass), fhe_mul_relin_workspace(ctx, pass) and
+ * fhe_rotate_workspace(ctx, pass) bytes are sufficient at every level (a level's regions are never
+ * larger than the top level's); fhe_keyswitch_pass_batch governs the passes at every level.
+ * Capture-safe like the top-level forms.
+ * Top-level only (their current errors for fewer limbs): fhe_rotate_hoisted, the rotation sums,
+ * fhe_linear_transform, and the multi-GPU (_shard, _dist, _loopback) forms.  There is no
+ * level-switching plaintext multiply. */
+int fhe_keyswitch_level(const fhe_ctx* ctx, uint64_t* ks0, uint64_t* ks1, const uint64_t* d2,
+                        const uint64_t* evk_b, const uint64_t* evk_a, uint32_t level,
+                        uint32_t batch, void* workspace, fhe_stream_t stream);
+int fhe_mul_relin_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* a, const uint64_t* b,
+                        const uint64_t* evk_b, const uint64_t* evk_a, uint32_t level,
+                        uint32_t batch, int rescale, void* workspace, fhe_stream_t stream);
+int fhe_rotate_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* in, uint32_t galois_elt,
+                     const uint64_t* rot_b, const uint64_t* rot_a, uint32_t level, uint32_t batch,
+                     void* workspace, fhe_stream_t stream);
 
 /* ---- multi-GPU: the limb-sharded key-switch over RCCL ---------------------
  * One process per GPU.  Rank r of G owns Q-limbs [r c, min((r + 1) c, L)), c = ceil(L / G)

@@ -307,17 +307,20 @@ class Evaluator {
     check(fhe_decrypt(ctx_.get(), pt.data(), ct.data(), sk.s.data(), 1, ct.limbs, s_), "fhe_decrypt");
     return pt;
   }
-  // Relin(a x b), optionally rescaled; NTT form over L limbs in.
+  // Relin(a x b), optionally rescaled; NTT form over l limbs in, 1 <= l <= L
+  // (the level is the ciphertexts' limb count; rk is the top-level key at every level), l or
+  // l - 1 limbs out.
   Ciphertext mul_relin(const Ciphertext& a, const Ciphertext& b, const SwitchKey& rk, bool rescale) const {
     same(a, b, "mul_relin");
-    if (a.components != 2 || !a.ntt_form || a.limbs != ctx_.L())
-      throw Error(FHE_EINVAL, "mul_relin: need 2-component NTT-form ciphertexts over L limbs");
-    Ciphertext out(ctx_, 2, ctx_.L() - (rescale ? 1 : 0), true);
+    if (a.components != 2 || !a.ntt_form || a.limbs < 1 || a.limbs > ctx_.L())
+      throw Error(FHE_EINVAL, "mul_relin: need 2-component NTT-form ciphertexts over 1 .. L limbs");
+    if (rescale && a.limbs < 2) throw Error(FHE_EINVAL, "mul_relin: rescale needs at least 2 limbs");
+    Ciphertext out(ctx_, 2, a.limbs - (rescale ? 1 : 0), true);
     const size_t need = fhe_mul_relin_workspace(ctx_.get(), 1);
     if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
-    check(fhe_mul_relin(ctx_.get(), out.data(), a.data(), b.data(), rk.b(), rk.a(), 1, rescale ? 1 : 0,
-                        ws_.data(), s_),
-          "fhe_mul_relin");
+    check(fhe_mul_relin_level(ctx_.get(), out.data(), a.data(), b.data(), rk.b(), rk.a(), a.limbs, 1,
+                              rescale ? 1 : 0, ws_.data(), s_),
+          "fhe_mul_relin_level");
     return out;
   }
   // Divide-and-round by the last modulus: drops one limb, keeps the form.
@@ -340,28 +343,29 @@ class Evaluator {
       if (e & 1) g = g * b % two_n;
     return (uint32_t)g;
   }
-  // Rotation of a 2-component NTT-form ciphertext over all L limbs by Galois element k, with the
-  // key-switch key from sigma_k(s) to s (NTT form [dnum][L+K][N]).
+  // Rotation of a 2-component NTT-form ciphertext over l limbs (1 <= l <= L, its level) by Galois
+  // element k, with the top-level key-switch key from sigma_k(s) to s (NTT form [dnum][L+K][N]).
   Ciphertext rotate(const Ciphertext& ct, uint32_t galois_elt, const DeviceBuffer& rot_b,
                     const DeviceBuffer& rot_a) const {
-    if (ct.components != 2 || !ct.ntt_form || ct.limbs != ctx_.L())
-      throw Error(FHE_EINVAL, "rotate: need a 2-component NTT-form ciphertext over L limbs");
+    if (ct.components != 2 || !ct.ntt_form || ct.limbs < 1 || ct.limbs > ctx_.L())
+      throw Error(FHE_EINVAL, "rotate: need a 2-component NTT-form ciphertext over 1 .. L limbs");
     Ciphertext out(ctx_, 2, ct.limbs, true);
     const size_t need = fhe_rotate_workspace(ctx_.get(), 1);
     if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
-    check(fhe_rotate(ctx_.get(), out.data(), ct.data(), galois_elt, rot_b.data(), rot_a.data(), 1,
-                     ws_.data(), s_),
-          "fhe_rotate");
+    check(fhe_rotate_level(ctx_.get(), out.data(), ct.data(), galois_elt, rot_b.data(), rot_a.data(),
+                           ct.limbs, 1, ws_.data(), s_),
+          "fhe_rotate_level");
     return out;
   }
   Ciphertext rotate(const Ciphertext& ct, uint32_t galois_elt, const SwitchKey& key) const {
-    if (ct.components != 2 || !ct.ntt_form || ct.limbs != ctx_.L())
-      throw Error(FHE_EINVAL, "rotate: need a 2-component NTT-form ciphertext over L limbs");
+    if (ct.components != 2 || !ct.ntt_form || ct.limbs < 1 || ct.limbs > ctx_.L())
+      throw Error(FHE_EINVAL, "rotate: need a 2-component NTT-form ciphertext over 1 .. L limbs");
     Ciphertext out(ctx_, 2, ct.limbs, true);
     const size_t need = fhe_rotate_workspace(ctx_.get(), 1);
     if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
-    check(fhe_rotate(ctx_.get(), out.data(), ct.data(), galois_elt, key.b(), key.a(), 1, ws_.data(), s_),
-          "fhe_rotate");
+    check(fhe_rotate_level(ctx_.get(), out.data(), ct.data(), galois_elt, key.b(), key.a(), ct.limbs,
+                           1, ws_.data(), s_),
+          "fhe_rotate_level");
     return out;
   }
   // Several rotations of one ciphertext sharing a single ModUp (fhe_rotate_hoisted); output r
