@@ -411,6 +411,15 @@ int fhe_rotate_hoisted(const fhe_ctx* c, uint64_t* out, const uint64_t* in,
                        fhe_stream_t s) {
   int rc = check_window(c, 0, c ? c->L : 0, c ? c->L : 0, "fhe_rotate_hoisted");
   if (rc) return rc;
+  return fhe_rotate_hoisted_level(c, out, in, galois_elts, rot_b, rot_a, c->L, count, batch, ws, s);
+}
+
+int fhe_rotate_hoisted_level(const fhe_ctx* c, uint64_t* out, const uint64_t* in,
+                             const uint32_t* galois_elts, const uint64_t* const* rot_b,
+                             const uint64_t* const* rot_a, uint32_t level, uint32_t count,
+                             uint32_t batch, void* ws, fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_rotate_hoisted_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_rotate_hoisted_level"))) return rc;
   if (count && (!galois_elts || !rot_b || !rot_a)) {
     set_error("fhe_rotate_hoisted: null Galois element or key array");
     return kInvalid;
@@ -420,13 +429,14 @@ int fhe_rotate_hoisted(const fhe_ctx* c, uint64_t* out, const uint64_t* in,
       set_error("fhe_rotate_hoisted: null key pointer for rotation " + std::to_string(r));
       return kInvalid;
     }
-  const uint64_t span = (uint64_t)count * batch * 2 * c->L * c->n;
-  if (span && in < out + span && out < in + (uint64_t)batch * 2 * c->L * c->n) {
+  const uint64_t span = (uint64_t)count * batch * 2 * level * c->n;
+  if (span && in < out + span && out < in + (uint64_t)batch * 2 * level * c->n) {
     set_error("fhe_rotate_hoisted: out must not overlap in");
     return kInvalid;
   }
   if ((rc = ensure_ws(c, rotate_hoisted_workspace_bytes(c, batch), &ws, hs(s)))) return rc;
-  return launch_rotate_hoisted(c, out, in, galois_elts, rot_b, rot_a, count, batch, ws, hs(s));
+  return launch_rotate_hoisted(c, out, in, galois_elts, rot_b, rot_a, level, count, batch, ws,
+                               hs(s));
 }
 
 size_t fhe_rotate_sum_hoisted_workspace(const fhe_ctx* c, uint32_t batch) {
@@ -439,6 +449,18 @@ int fhe_rotate_sum_hoisted(const fhe_ctx* c, uint64_t* out, const uint64_t* in,
                            uint32_t count, uint32_t batch, void* ws, fhe_stream_t s) {
   int rc = check_window(c, 0, c ? c->L : 0, c ? c->L : 0, "fhe_rotate_sum_hoisted");
   if (rc) return rc;
+  return fhe_rotate_sum_hoisted_level(c, out, in, galois_elts, rot_b, rot_a, pt, c->L, count, batch,
+                                      ws, s);
+}
+
+int fhe_rotate_sum_hoisted_level(const fhe_ctx* c, uint64_t* out, const uint64_t* in,
+                                 const uint32_t* galois_elts, const uint64_t* const* rot_b,
+                                 const uint64_t* const* rot_a, const uint64_t* const* pt,
+                                 uint32_t level, uint32_t count, uint32_t batch, void* ws,
+                                 fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_rotate_sum_hoisted_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_rotate_sum_hoisted_level")))
+    return rc;
   if (count == 0 || count > kRotSumMax) {
     set_error("fhe_rotate_sum_hoisted: count must be 1..16");
     return kInvalid;
@@ -456,14 +478,14 @@ int fhe_rotate_sum_hoisted(const fhe_ctx* c, uint64_t* out, const uint64_t* in,
       return kInvalid;
     }
   }
-  const uint64_t span = (uint64_t)batch * 2 * c->L * c->n;
+  const uint64_t span = (uint64_t)batch * 2 * level * c->n;
   if (spans_overlap(out, span, in, span)) {
     set_error("fhe_rotate_sum_hoisted: out must not overlap in");
     return kInvalid;
   }
   if ((rc = ensure_ws(c, rotate_sum_hoisted_workspace_bytes(c, batch), &ws, hs(s)))) return rc;
-  return launch_rotate_sum_hoisted(c, out, in, galois_elts, rot_b, rot_a, pt, count, batch, ws,
-                                   hs(s));
+  return launch_rotate_sum_hoisted(c, out, in, galois_elts, rot_b, rot_a, pt, level, count, batch,
+                                   ws, hs(s));
 }
 
 size_t fhe_rotate_sum_multi_workspace(const fhe_ctx* c, uint32_t count, uint32_t batch) {
@@ -476,6 +498,17 @@ int fhe_rotate_sum_multi(const fhe_ctx* c, uint64_t* out, const uint64_t* const*
                          fhe_stream_t s) {
   int rc = check_window(c, 0, c ? c->L : 0, c ? c->L : 0, "fhe_rotate_sum_multi");
   if (rc) return rc;
+  return fhe_rotate_sum_multi_level(c, out, cts, galois_elts, rot_b, rot_a, c->L, count, batch, ws,
+                                    s);
+}
+
+int fhe_rotate_sum_multi_level(const fhe_ctx* c, uint64_t* out, const uint64_t* const* cts,
+                               const uint32_t* galois_elts, const uint64_t* const* rot_b,
+                               const uint64_t* const* rot_a, uint32_t level, uint32_t count,
+                               uint32_t batch, void* ws, fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_rotate_sum_multi_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_rotate_sum_multi_level")))
+    return rc;
   if (count == 0 || count > kRotSumMax) {
     set_error("fhe_rotate_sum_multi: count must be 1..16");
     return kInvalid;
@@ -485,7 +518,7 @@ int fhe_rotate_sum_multi(const fhe_ctx* c, uint64_t* out, const uint64_t* const*
     set_error("fhe_rotate_sum_multi: null Galois element, ciphertext or key array");
     return kInvalid;
   }
-  const uint64_t span = (uint64_t)batch * 2 * c->L * c->n;
+  const uint64_t span = (uint64_t)batch * 2 * level * c->n;
   for (uint32_t r = 0; r < count; ++r) {
     if (!cts[r] || (galois_elts[r] != 1 && (!rot_b[r] || !rot_a[r]))) {
       set_error("fhe_rotate_sum_multi: null ciphertext or key pointer for term " +
@@ -499,7 +532,8 @@ int fhe_rotate_sum_multi(const fhe_ctx* c, uint64_t* out, const uint64_t* const*
     }
   }
   if ((rc = ensure_ws(c, rotate_sum_multi_workspace_bytes(c, count, batch), &ws, hs(s)))) return rc;
-  return launch_rotate_sum_multi(c, out, cts, galois_elts, rot_b, rot_a, count, batch, ws, hs(s));
+  return launch_rotate_sum_multi(c, out, cts, galois_elts, rot_b, rot_a, level, count, batch, ws,
+                                 hs(s));
 }
 
 size_t fhe_linear_transform_workspace(const fhe_ctx* c, uint32_t n2, uint32_t batch) {
@@ -513,6 +547,19 @@ int fhe_linear_transform(const fhe_ctx* c, uint64_t* out, const uint64_t* in, ui
                          const uint64_t* const* pt, uint32_t batch, void* ws, fhe_stream_t s) {
   int rc = check_window(c, 0, c ? c->L : 0, c ? c->L : 0, "fhe_linear_transform");
   if (rc) return rc;
+  return fhe_linear_transform_level(c, out, in, n1, n2, baby_elts, baby_b, baby_a, giant_elts,
+                                    giant_b, giant_a, pt, c->L, batch, ws, s);
+}
+
+int fhe_linear_transform_level(const fhe_ctx* c, uint64_t* out, const uint64_t* in, uint32_t n1,
+                               uint32_t n2, const uint32_t* baby_elts,
+                               const uint64_t* const* baby_b, const uint64_t* const* baby_a,
+                               const uint32_t* giant_elts, const uint64_t* const* giant_b,
+                               const uint64_t* const* giant_a, const uint64_t* const* pt,
+                               uint32_t level, uint32_t batch, void* ws, fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_linear_transform_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_linear_transform_level")))
+    return rc;
   if (n1 == 0 || n1 > kRotSumMax || n2 == 0 || n2 > kRotSumMax) {
     set_error("fhe_linear_transform: n1 and n2 must be 1..16");
     return kInvalid;
@@ -535,14 +582,14 @@ int fhe_linear_transform(const fhe_ctx* c, uint64_t* out, const uint64_t* in, ui
       set_error("fhe_linear_transform: null plaintext pointer " + std::to_string(r));
       return kInvalid;
     }
-  const uint64_t span = (uint64_t)batch * 2 * c->L * c->n;
+  const uint64_t span = (uint64_t)batch * 2 * level * c->n;
   if (spans_overlap(out, span, in, span)) {
     set_error("fhe_linear_transform: out must not overlap in");
     return kInvalid;
   }
   if ((rc = ensure_ws(c, linear_transform_workspace_bytes(c, n2, batch), &ws, hs(s)))) return rc;
   return launch_linear_transform(c, out, in, n1, n2, baby_elts, baby_b, baby_a, giant_elts, giant_b,
-                                 giant_a, pt, batch, ws, hs(s));
+                                 giant_a, pt, level, batch, ws, hs(s));
 }
 
 size_t fhe_mul_relin_workspace(const fhe_ctx* c, uint32_t batch) {

@@ -125,6 +125,13 @@ inline u32 modinv_odd_pow2(u32 k, u32 bits) {
 // gather maps every aligned 64-slot block onto one aligned 64-slot block (brv(src) =
 // brv(i) k + (k - 1) / 2 mod N: the top bits of brv(i) only reach the top bits of the product),
 // so each wavefront's gathered loads stay within 512 contiguous bytes.
+// Levels (LVL): rows = nq + K with nq < L live Q-limbs.  The accumulators, cadd, ext and in are
+// dense over these rows; the keys [dnum][L + K][N] and the plaintexts [L + K][N] are the top-level
+// tensors read in place: digit stride kds words, row r at key / plaintext row krow = r (Q rows) or
+// kprow + (r - nq) (special rows), which is also row r's limb (mods[krow]).  krow only moves whole
+// rows, so the gather property above holds at every level.  The top level (kds = rows N, kprow =
+// nq = L, krow = r) takes the !LVL instantiations, which ignore kds / kprow: as one kernel the two
+// extra uniform values cost registers the FAST dnum = 4 form does not have to spare.
 struct RotSumTerms {
   u32 count;
   u32 gal[kRotSumMax];
@@ -173,15 +180,16 @@ __device__ __forceinline__ void rs_mac61(u128& a, u64 x, u64 y) {
 // shared by the kRotSumBC ciphertexts), so (p R)(t R^-1) = p t adds into the 128-bit sums with
 // one mul_wide61 (operands below 2q < 2^61; 16 terms of 4 q^2 stay below 2^126).  Against the u128
 // form: 2 x 4 u128 products and 2 reduce128 per term and ciphertext become 2 dot_wide61 + 2 REDC.
-template <int DNUM, bool WIDE, bool FAST = false>
+template <int DNUM, bool WIDE, bool FAST = false, bool LVL = false>
 __global__ __launch_bounds__(kThreads) void k_rot_sum(u64* __restrict__ acc, u64 acc_ws,
                                                       u64* __restrict__ cadd, int flags,
                                                       const u64* __restrict__ ext0,
                                                       const u64* __restrict__ in0,
-                                                      const RotSumTerms tm, u32 rows, u32 L,
+                                                      const RotSumTerms tm, u32 rows, u32 nq,
                                                       u32 alpha, u32 batch, u32 log_n,
-                                                      const ModParams* __restrict__ mods) {
-  const u64 n = 1ull << log_n, rn = (u64)rows * n, ln = (u64)L * n;
+                                                      const ModParams* __restrict__ mods, u64 kds,
+                                                      u32 kprow) {
+  const u64 n = 1ull << log_n, rn = (u64)rows * n, ln = (u64)nq * n;
   const u32 per_row = (u32)(n / kThreads), nbc = (batch + kRotSumBC - 1) / kRotSumBC;
   const u32 xcd = blockIdx.x % 8, k8 = blockIdx.x / 8;
   const u32 bc = k8 % nbc, item = (k8 / nbc) * 8 + xcd;
@@ -189,19 +197,23 @@ __global__ __launch_bounds__(kThreads) void k_rot_sum(u64* __restrict__ acc, u64
   const u32 r = item / per_row;
   const u64 i = (u64)(item % per_row) * kThreads + threadIdx.x;
   const u64 e = (u64)r * n + i;
-  const ModParams m = mods[r];  // rows = the context's L + K limbs in order
-  const u32 own = r < L ? r / alpha : 0xffffffffu;
+  // (r + (kprow - nq) [r >= nq] in min / max arithmetic, as k_ks_row_inner: workgroup-uniform)
+  const u32 krow = LVL ? r + (kprow - nq) * min(1u, max(r + 1, nq) - nq) : r;
+  const u64 ke = LVL ? (u64)krow * n + i : e;
+  const u64 kd = LVL ? kds : rn;
+  const ModParams m = mods[krow];
+  const u32 own = r < nq ? r / alpha : 0xffffffffu;
   const u32 b0 = bc * kRotSumBC, nb = min(kRotSumBC, batch - b0);
   u128 s0[kRotSumBC] = {}, s1[kRotSumBC] = {}, a0[kRotSumBC] = {}, a1[kRotSumBC] = {};
   const bool ident = (flags & kRotSumC1) != 0;
   const u32 sh = 32 - log_n, mask2 = (2u << log_n) - 1;
   for (u32 k = 0; k < tm.count; ++k) {
     const u32 g = tm.gal[k];
-    const u64 p = tm.pt[k] ? tm.pt[k][e] : 1;  // no plaintext: the term itself (rotate_sum_multi)
+    const u64 p = tm.pt[k] ? tm.pt[k][ke] : 1;  // no plaintext: the term itself (rotate_sum_multi)
     const u64* __restrict__ in = tm.in[k] ? tm.in[k] : in0;
     const u64* __restrict__ ext = tm.ext[k] ? tm.ext[k] : ext0;
     if (g == 1) {  // the unrotated term (workgroup-uniform)
-      if (r < L) {
+      if (r < nq) {
 #pragma unroll
         for (u32 bb = 0; bb < kRotSumBC; ++bb) {
           if (bb >= nb) break;
@@ -223,8 +235,8 @@ __global__ __launch_bounds__(kThreads) void k_rot_sum(u64* __restrict__ acc, u64
     u64 kb[DNUM], ka[DNUM];
 #pragma unroll
     for (int j = 0; j < DNUM; ++j) {
-      kb[j] = tm.kb[k][(u64)j * rn + e];
-      ka[j] = tm.ka[k][(u64)j * rn + e];
+      kb[j] = tm.kb[k][(u64)j * kd + ke];
+      ka[j] = tm.ka[k][(u64)j * kd + ke];
     }
     if constexpr (FAST) {
       static_assert(!WIDE && DNUM <= 4, "FAST: narrow moduli, dot_wide61 of <= 4 terms");
@@ -244,7 +256,7 @@ __global__ __launch_bounds__(kThreads) void k_rot_sum(u64* __restrict__ acc, u64
         rs_mac61(s0[bb], pr, mont_redc_x(lo, hi, m.q, qi));
         dot_wide61<DNUM>(x, ka, lo, hi);
         rs_mac61(s1[bb], pr, mont_redc_x(lo, hi, m.q, qi));
-        if (r < L) rs_mac61(a0[bb], p, in[(u64)b * 2 * ln + es]);
+        if (r < nq) rs_mac61(a0[bb], p, in[(u64)b * 2 * ln + es]);
       }
       continue;
     }
@@ -262,7 +274,7 @@ __global__ __launch_bounds__(kThreads) void k_rot_sum(u64* __restrict__ acc, u64
       }
       rs_mac<WIDE>(s0[bb], p, rs_fin<WIDE>(t0, m), m);
       rs_mac<WIDE>(s1[bb], p, rs_fin<WIDE>(t1, m), m);
-      if (r < L) rs_mac<WIDE>(a0[bb], p, in[(u64)b * 2 * ln + es], m);
+      if (r < nq) rs_mac<WIDE>(a0[bb], p, in[(u64)b * 2 * ln + es], m);
     }
   }
 #pragma unroll
@@ -271,7 +283,7 @@ __global__ __launch_bounds__(kThreads) void k_rot_sum(u64* __restrict__ acc, u64
     const u32 b = b0 + bb;
     acc[(u64)b * rn + e] = rs_fin<WIDE>(s0[bb], m);
     acc[acc_ws + (u64)b * rn + e] = rs_fin<WIDE>(s1[bb], m);
-    if (r < L) {
+    if (r < nq) {
       cadd[(u64)b * ln + e] = rs_fin<WIDE>(a0[bb], m);
       if (ident) cadd[(u64)(batch + b) * ln + e] = rs_fin<WIDE>(a1[bb], m);
     }
@@ -443,11 +455,17 @@ size_t rotate_hoisted_workspace_bytes(const fhe_ctx* c, u32 batch) {
 // there too on the fused ModDown; a separate sigma(c0) pass on the wide contexts).
 // Restated by oracle/pyoracle.py rotate_hoisted; decrypts to sigma_k(m) like fhe_rotate, but is
 // not bit-identical to it (ModUp of sigma(c1) vs sigma of ModUp(c1)).
+// `level` Q-limbs (1 .. c->L) in in / out: the regions below are laid out for that many, the keys
+// stay the top-level ones (rotate_hoisted_workspace_bytes, sized for c->L, covers every level).
 int launch_rotate_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* galois,
-                          const u64* const* rot_b, const u64* const* rot_a, u32 count, u32 batch,
-                          void* ws, hipStream_t s) {
+                          const u64* const* rot_b, const u64* const* rot_a, u32 level, u32 count,
+                          u32 batch, void* ws, hipStream_t s) {
   if (c->K == 0) {
     set_error("rotate_hoisted: context has no special primes (K = 0)");
+    return kInvalid;
+  }
+  if (level == 0 || level > c->L) {
+    set_error("rotate_hoisted: level must be in [1, L]");
     return kInvalid;
   }
   const u32 two_n = 2u << c->log_n;
@@ -457,7 +475,7 @@ int launch_rotate_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* 
       return kInvalid;
     }
   if (batch == 0 || count == 0) return kOk;
-  const u32 L = c->L;
+  const u32 L = level;  // the live Q-limbs
   const u64 n = c->n, ln = (u64)L * n;
   u64* c1 = static_cast<u64*>(ws);  // [batch][L][N] NTT form
   u64* c_all = c1 + batch * ln;     // [batch][L][N] coefficient form
@@ -471,14 +489,15 @@ int launch_rotate_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* 
   // conversion pass (rns.hip hoist_up)
   const bool prep = ks_prepared(c);
   if ((rc = launch_ntt_strided(c, false, c1, ln, c_all, ln, batch, 0, L, s,
-                               prep ? c->d_nfold_up : nullptr, prep && ks_split30(c))))
+                               prep ? ks_level_nfold_up(c, level) : nullptr,
+                               prep && ks_split30(c))))
     return rc;
   CAll call = CAll::contiguous(c_all, L, n);
   call.scaled = prep;
   KsHoist up;
   up.modup_only = true;
   if ((rc = launch_keyswitch_shard(c, nullptr, nullptr, call, c1, nullptr, nullptr, 0, L, batch,
-                                   kws, s, nullptr, &up)))
+                                   kws, s, nullptr, &up, level)))
     return rc;
   for (u32 r = 0; r < count; ++r) {
     u64* o = out + (u64)r * batch * 2 * ln;
@@ -498,7 +517,7 @@ int launch_rotate_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* 
       ep.add_bs = ln;
     }
     if ((rc = launch_keyswitch_shard(c, o, o + ln, call, c1, rot_b[r], rot_a[r], 0, L, batch, kws,
-                                     s, &ep, &h)))
+                                     s, &ep, &h, level)))
       return rc;
   }
   return kOk;
@@ -512,26 +531,34 @@ size_t rotate_sum_hoisted_workspace_bytes(const fhe_ctx* c, u32 batch) {
 }
 
 namespace {
-// The rotation sums' workspace regions (rotate_sum_hoisted_workspace_bytes)
+// The rotation sums' workspace regions (rotate_sum_hoisted_workspace_bytes), laid out for the
+// call's `level` live Q-limbs (L below) and its ceil(level / alpha) live digits: never more than
+// the top level's
 struct RotSumWs {
   u64* c_all;  // [batch][L][N] coefficient form of the c1 being ModUp'ed
   u64* cadd;   // [2][batch][L][N]: the c0 sum, then the unrotated terms' c1 sum
   u64* ydn;    // [2 batch][K][N] the fused ModDown's INTT output
   u64* kws;    // key-switch workspace: ext [dnum][batch][L + K][N], then the accumulators
+  u32 level;   // the live Q-limbs
 };
-RotSumWs rotsum_ws(const fhe_ctx* c, void* ws, u32 batch) {
-  const u64 ln = (u64)c->L * c->n;
+RotSumWs rotsum_ws(const fhe_ctx* c, void* ws, u32 level, u32 batch) {
+  const u64 ln = (u64)level * c->n;
   RotSumWs w;
   w.c_all = static_cast<u64*>(ws);
   w.cadd = w.c_all + batch * ln;
   w.ydn = w.cadd + 2 * batch * ln;
   w.kws = w.ydn + 2 * batch * (u64)c->K * c->n;
+  w.level = level;
   return w;
 }
 
-int rotsum_check(const fhe_ctx* c, u32 count, const u32* galois, const char* who) {
+int rotsum_check(const fhe_ctx* c, u32 level, u32 count, const u32* galois, const char* who) {
   if (c->K == 0) {
     set_error(std::string(who) + ": context has no special primes (K = 0)");
+    return kInvalid;
+  }
+  if (level == 0 || level > c->L) {
+    set_error(std::string(who) + ": level must be in [1, L]");
     return kInvalid;
   }
   if (count > kRotSumMax) {
@@ -552,56 +579,73 @@ int rotsum_check(const fhe_ctx* c, u32 count, const u32* galois, const char* who
 }
 
 // ModUp of in's c1 ([batch][2][L][N], NTT form) into the ext region at kws (w.kws, or another
-// region of ext_words(c, batch) words: a ModUp-only key-switch writes nothing past its digits):
+// region of ext_words(c, level, batch) words: a ModUp-only key-switch writes nothing past its digits):
 // the prepared INTT (the fused hoisted ModUp's scaled inputs) and the hoisted ModUp (rns.hip,
 // modup_only)
-u64 ext_words(const fhe_ctx* c, u32 batch) {
-  return (u64)c->dnum * batch * (c->L + c->K) * c->n;
+u64 ext_words(const fhe_ctx* c, u32 level, u32 batch) {
+  return (u64)ks_level_digits(c, level) * batch * (level + c->K) * c->n;
 }
 int rotsum_modup(const fhe_ctx* c, const u64* in, u32 batch, const RotSumWs& w, hipStream_t s,
                  u64* kws = nullptr) {
-  const u32 L = c->L;
+  const u32 L = w.level;
   const u64 ln = (u64)L * c->n;
   const bool prep = ks_prepared(c);
   if (int rc = launch_ntt_strided(c, false, in + ln, 2 * ln, w.c_all, ln, batch, 0, L, s,
-                                  prep ? c->d_nfold_up : nullptr, prep && ks_split30(c)))
+                                  prep ? ks_level_nfold_up(c, L) : nullptr,
+                                  prep && ks_split30(c)))
     return rc;
   CAll call = CAll::contiguous(w.c_all, L, c->n);
   call.scaled = prep;
   KsHoist up;
   up.modup_only = true;
   return launch_keyswitch_shard(c, nullptr, nullptr, call, in + ln, nullptr, nullptr, 0, L, batch,
-                                kws ? kws : w.kws, s, nullptr, &up);
+                                kws ? kws : w.kws, s, nullptr, &up, L);
 }
 
 // One k_rot_sum launch over the terms tm of ciphertexts in (whose ModUp is in the ext region when
 // a term is rotated): the accumulators and cadd get the sums (flags: kRotSumC1)
 int rotsum_pass(const fhe_ctx* c, const u64* in, const RotSumTerms& tm, int flags, u32 batch,
                 const RotSumWs& w, hipStream_t s) {
-  const u32 L = c->L, rows = L + c->K;
+  const u32 L = w.level, rows = L + c->K, dl = ks_level_digits(c, L);
   const u64 n = c->n;
+  // the top-level keys and plaintexts in place: digit stride (c->L + K) N, special rows from c->L
+  const u64 kds = (u64)(c->L + c->K) * n;
+  const u32 kprow = c->L;
+  const bool fast = c->lz16 && c->dnum <= 4;
   const u64 blocks = (u64)rows * (n / kThreads);
   const u64 grid = (blocks + 7) / 8 * 8 * ((batch + kRotSumBC - 1) / kRotSumBC);
   if (int rc = check_grid(grid, kThreads, 1, 1, "rotate_sum")) return rc;
-  u64* acc = ks_acc_region(c, w.kws, L, batch);
+  u64* acc = ks_acc_region(c, w.kws, L, batch, L);
   const u64 acc_ws = (u64)batch * rows * n;
   const u64* ext = w.kws;
-  switch (c->dnum) {
-#define X(d)                                                                                      \
-  case d:                                                                                         \
-    if (c->wide)                                                                                  \
-      k_rot_sum<d, true><<<dim3((u32)grid), kThreads, 0, s>>>(                                    \
-          acc, acc_ws, w.cadd, flags, ext, in, tm, rows, L, c->alpha, batch, c->log_n, c->d_mods);\
-    else if (c->lz16 && d <= 4)                                                                   \
-      k_rot_sum<(d <= 4 ? d : 4), false, true><<<dim3((u32)grid), kThreads, 0, s>>>(              \
-          acc, acc_ws, w.cadd, flags, ext, in, tm, rows, L, c->alpha, batch, c->log_n, c->d_mods);\
+  // the live digits choose the instantiation; FAST stays a property of the context (fast above);
+  // LVL below the top level only
+  const bool lvl = L != c->L;
+#define RS(d, W, F)                                                                               \
+  do {                                                                                            \
+    if (lvl)                                                                                      \
+      k_rot_sum<d, W, F, true><<<dim3((u32)grid), kThreads, 0, s>>>(                              \
+          acc, acc_ws, w.cadd, flags, ext, in, tm, rows, L, c->alpha, batch, c->log_n, c->d_mods, \
+          kds, kprow);                                                                            \
     else                                                                                          \
-      k_rot_sum<d, false><<<dim3((u32)grid), kThreads, 0, s>>>(                                   \
-          acc, acc_ws, w.cadd, flags, ext, in, tm, rows, L, c->alpha, batch, c->log_n, c->d_mods);\
+      k_rot_sum<d, W, F, false><<<dim3((u32)grid), kThreads, 0, s>>>(                             \
+          acc, acc_ws, w.cadd, flags, ext, in, tm, rows, L, c->alpha, batch, c->log_n, c->d_mods, \
+          kds, kprow);                                                                            \
+  } while (0)
+  switch (dl) {
+#define X(d)                                     \
+  case d:                                        \
+    if (c->wide)                                 \
+      RS(d, true, false);                        \
+    else if (fast && d <= 4)                     \
+      RS((d <= 4 ? d : 4), false, true);         \
+    else                                         \
+      RS(d, false, false);                       \
     break;
     X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
 #undef X
   }
+#undef RS
   FHE_HIP_CHECK(hipGetLastError());
   prof_mark(s, "rot_sum");
   return kOk;
@@ -611,7 +655,7 @@ int rotsum_pass(const fhe_ctx* c, const u64* in, const RotSumTerms& tm, int flag
 // terms' c1 sum (c1) in its finish
 int rotsum_moddown(const fhe_ctx* c, u64* out, const u64* d2ref, bool c1, u32 batch,
                    const RotSumWs& w, hipStream_t s) {
-  const u32 L = c->L;
+  const u32 L = w.level;
   const u64 ln = (u64)L * c->n;
   KsHoist h;
   h.acc_ready = true;
@@ -622,7 +666,7 @@ int rotsum_moddown(const fhe_ctx* c, u64* out, const u64* d2ref, bool c1, u32 ba
   ep.add1 = c1 ? w.cadd + batch * ln : nullptr;
   ep.add_bs = ln;
   return launch_keyswitch_shard(c, out, out + ln, CAll::contiguous(w.c_all, L, c->n), d2ref,
-                                nullptr, nullptr, 0, L, batch, w.kws, s, &ep, &h);
+                                nullptr, nullptr, 0, L, batch, w.kws, s, &ep, &h, L);
 }
 }  // namespace
 
@@ -634,9 +678,9 @@ int rotsum_moddown(const fhe_ctx* c, u64* out, const u64* d2ref, bool c1, u32 ba
 // output round trip.  Restated by oracle/pyoracle.py rotate_sum_hoisted.
 int launch_rotate_sum_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* galois,
                               const u64* const* rot_b, const u64* const* rot_a,
-                              const u64* const* pt, u32 count, u32 batch, void* ws,
+                              const u64* const* pt, u32 level, u32 count, u32 batch, void* ws,
                               hipStream_t s) {
-  if (int rc = rotsum_check(c, count, galois, "rotate_sum_hoisted")) return rc;
+  if (int rc = rotsum_check(c, level, count, galois, "rotate_sum_hoisted")) return rc;
   RotSumTerms tm{};
   tm.count = count;
   bool ident = false, rotated = false;
@@ -649,22 +693,22 @@ int launch_rotate_sum_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u
     rotated = rotated || galois[r] != 1;
   }
   if (batch == 0) return kOk;
-  const RotSumWs w = rotsum_ws(c, ws, batch);
+  const RotSumWs w = rotsum_ws(c, ws, level, batch);
   int rc;
   if (rotated && (rc = rotsum_modup(c, in, batch, w, s))) return rc;
   if ((rc = rotsum_pass(c, in, tm, ident ? kRotSumC1 : 0, batch, w, s))) return rc;
-  return rotsum_moddown(c, out, in + (u64)c->L * c->n, ident, batch, w, s);
+  return rotsum_moddown(c, out, in + (u64)level * c->n, ident, batch, w, s);
 }
 
 size_t rotate_sum_multi_workspace_bytes(const fhe_ctx* c, u32 count, u32 batch) {
   // the rotation sum's workspace, then the ModUp digits of every rotated term past the first
   return rotate_sum_hoisted_workspace_bytes(c, batch) +
-         (size_t)(count > 1 ? count - 1 : 0) * ext_words(c, batch) * sizeof(u64);
+         (size_t)(count > 1 ? count - 1 : 0) * ext_words(c, c->L, batch) * sizeof(u64);
 }
 
 namespace {
 // The giant-step sum: every rotated term's ModUp into its own digit region (the first in w's ext
-// region, the others in `extra`, ext_words each), then ONE k_rot_sum pass over all the terms (each
+// region, the others in `extra`, ext_words of w's level each), then ONE k_rot_sum pass over all the terms (each
 // with its own ciphertext and digits, no plaintext: the accumulators are written once) and ONE
 // ModDown.
 int rotsum_multi(const fhe_ctx* c, u64* out, const u64* const* cts, const u32* galois,
@@ -680,14 +724,14 @@ int rotsum_multi(const fhe_ctx* c, u64* out, const u64* const* cts, const u32* g
     tm.pt[r] = nullptr;
     tm.in[r] = cts[r];
     if (galois[r] == 1) continue;
-    u64* region = nrot == 0 ? w.kws : extra + (u64)(nrot - 1) * ext_words(c, batch);
+    u64* region = nrot == 0 ? w.kws : extra + (u64)(nrot - 1) * ext_words(c, w.level, batch);
     if (int rc = rotsum_modup(c, cts[r], batch, w, s, region)) return rc;
     tm.ext[r] = region;
     ++nrot;
   }
   int rc;
   if ((rc = rotsum_pass(c, cts[0], tm, kRotSumC1, batch, w, s))) return rc;
-  return rotsum_moddown(c, out, cts[0] + (u64)c->L * c->n, true, batch, w, s);
+  return rotsum_moddown(c, out, cts[0] + (u64)w.level * c->n, true, batch, w, s);
 }
 }  // namespace
 
@@ -697,14 +741,16 @@ int rotsum_multi(const fhe_ctx* c, u64* out, const u64* const* cts, const u32* g
 // accumulators with the sigma(c0) sum (and the unrotated terms' c0, c1) added in its finish.
 // Restated by oracle/pyoracle.py rotate_sum_multi.
 int launch_rotate_sum_multi(const fhe_ctx* c, u64* out, const u64* const* cts, const u32* galois,
-                            const u64* const* rot_b, const u64* const* rot_a, u32 count,
-                            u32 batch, void* ws, hipStream_t s) {
-  if (int rc = rotsum_check(c, count, galois, "rotate_sum_multi")) return rc;
+                            const u64* const* rot_b, const u64* const* rot_a, u32 level,
+                            u32 count, u32 batch, void* ws, hipStream_t s) {
+  if (int rc = rotsum_check(c, level, count, galois, "rotate_sum_multi")) return rc;
   if (batch == 0 || count == 0) return kOk;
+  // the extra digit regions start where the top level's do (past the rotation sum's top-level
+  // workspace) and are a level's ext_words each, so they end within the top-level size
   u64* extra = reinterpret_cast<u64*>(static_cast<char*>(ws) +
                                       rotate_sum_hoisted_workspace_bytes(c, batch));
-  return rotsum_multi(c, out, cts, galois, rot_b, rot_a, count, batch, rotsum_ws(c, ws, batch),
-                      extra, s);
+  return rotsum_multi(c, out, cts, galois, rot_b, rot_a, count, batch,
+                      rotsum_ws(c, ws, level, batch), extra, s);
 }
 
 size_t linear_transform_workspace_bytes(const fhe_ctx* c, u32 n2, u32 batch) {
@@ -722,17 +768,19 @@ size_t linear_transform_workspace_bytes(const fhe_ctx* c, u32 n2, u32 batch) {
 int launch_linear_transform(const fhe_ctx* c, u64* out, const u64* in, u32 n1, u32 n2,
                             const u32* baby, const u64* const* baby_b, const u64* const* baby_a,
                             const u32* giant, const u64* const* giant_b,
-                            const u64* const* giant_a, const u64* const* pt, u32 batch, void* ws,
-                            hipStream_t s) {
+                            const u64* const* giant_a, const u64* const* pt, u32 level,
+                            u32 batch, void* ws, hipStream_t s) {
   if (n1 == 0 || n2 == 0 || n1 > kRotSumMax || n2 > kRotSumMax) {
     set_error("linear_transform: n1 and n2 must be 1..16");
     return kInvalid;
   }
-  if (int rc = rotsum_check(c, n1, baby, "linear_transform")) return rc;
-  if (int rc = rotsum_check(c, n2, giant, "linear_transform")) return rc;
+  if (int rc = rotsum_check(c, level, n1, baby, "linear_transform")) return rc;
+  if (int rc = rotsum_check(c, level, n2, giant, "linear_transform")) return rc;
   if (batch == 0) return kOk;
-  const RotSumWs w = rotsum_ws(c, ws, batch);
-  const u64 ct_words = (u64)batch * 2 * c->L * c->n;
+  // the giant-step inputs and the extra digit regions start at the top level's offset and are laid
+  // out for `level` limbs: both end within linear_transform_workspace_bytes
+  const RotSumWs w = rotsum_ws(c, ws, level, batch);
+  const u64 ct_words = (u64)batch * 2 * level * c->n;
   u64* inner = reinterpret_cast<u64*>(static_cast<char*>(ws) +
                                       rotate_sum_hoisted_workspace_bytes(c, batch));
   u64* extra = inner + (u64)n2 * ct_words;
@@ -755,7 +803,7 @@ int launch_linear_transform(const fhe_ctx* c, u64* out, const u64* in, u32 n1, u
     }
     u64* ig = inner + (u64)g * ct_words;
     if ((rc = rotsum_pass(c, in, tm, ident ? kRotSumC1 : 0, batch, w, s)) ||
-        (rc = rotsum_moddown(c, ig, in + (u64)c->L * c->n, ident, batch, w, s)))
+        (rc = rotsum_moddown(c, ig, in + (u64)level * c->n, ident, batch, w, s)))
       return rc;
     inner_ptr[g] = ig;
   }

@@ -257,8 +257,11 @@ struct KsHoist {
 };
 // The key-switch workspace's regions (keyswitch_workspace_bytes): ext [dnum][batch][rows][N], then
 // the accumulators acc [2][batch][rows][N], rows = nlimbs + K
-inline u64* ks_acc_region(const fhe_ctx* c, void* ws, u32 nlimbs, u32 batch) {
-  return static_cast<u64*>(ws) + (u64)c->dnum * batch * (nlimbs + c->K) * c->n;
+// (level != 0: a level call's live digits in place of dnum)
+inline u32 ks_level_digits(const fhe_ctx* c, u32 level);
+inline u64* ks_acc_region(const fhe_ctx* c, void* ws, u32 nlimbs, u32 batch, u32 level = 0) {
+  const u64 dl = level ? ks_level_digits(c, level) : c->dnum;
+  return static_cast<u64*>(ws) + dl * batch * (nlimbs + c->K) * c->n;
 }
 struct ModDownRowArgs {
   const u64* conv;
@@ -348,10 +351,11 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
                            u32 nlimbs, u32 batch, void* ws, hipStream_t s,
                            const KsEpilogue* ep = nullptr, const KsHoist* hoist = nullptr,
                            u32 level = 0);
-// level != 0 (then limb0 = 0, nlimbs = level, no hoist): the key-switch over the first `level`
-// Q-limbs with the top-level digit width and the top-level key [dnum][L + K][N] read in place
-// (key rows {0 .. level-1} u {L .. L+K-1} of the digits j < ks_level_digits); call holds `level`
-// limbs, prepared with ks_level_nfold_up's table.  level == L is the top-level call itself.
+// level != 0 (then limb0 = 0, nlimbs = level): the key-switch over the first `level` Q-limbs with
+// the top-level digit width and the top-level key [dnum][L + K][N] read in place (key rows
+// {0 .. level-1} u {L .. L+K-1} of the digits j < ks_level_digits); call holds `level` limbs,
+// prepared with ks_level_nfold_up's table.  level == L is the top-level call itself.  The three
+// hoist modes (KsHoist) run over the same live limbs, digits and rows.
 inline u32 ks_level_digits(const fhe_ctx* c, u32 level) {
   return (level + c->alpha - 1) / c->alpha;
 }
@@ -412,9 +416,13 @@ int launch_rotate(const fhe_ctx* c, u64* out, const u64* in, u32 galois_elt, con
 size_t rotate_workspace_bytes(const fhe_ctx* c, u32 batch);
 // `count` rotations of the same ciphertexts sharing one ModUp: out [count][batch][2][L][N],
 // galois[r] with its key rot_b[r] / rot_a[r] (host arrays of device pointers)
+// (level, here and in the rotation sums and the linear transform below: the Q-limbs of the
+// ciphertexts, 1 .. L, in place of L in their layouts; the keys [dnum][L + K][N] and the plaintexts
+// [L + K][N] stay the top-level ones, read in place; the *_workspace_bytes, sized for L, cover
+// every level)
 int launch_rotate_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* galois,
-                          const u64* const* rot_b, const u64* const* rot_a, u32 count, u32 batch,
-                          void* ws, hipStream_t s);
+                          const u64* const* rot_b, const u64* const* rot_a, u32 level, u32 count,
+                          u32 batch, void* ws, hipStream_t s);
 size_t rotate_hoisted_workspace_bytes(const fhe_ctx* c, u32 batch);
 // Double-hoisted rotation sum: out [batch][2][L][N] = sum_r pt[r] rot_{galois[r]}(in), one ModUp
 // and one ModDown; pt[r] [L + K][N] NTT form (host array of device pointers); galois[r] == 1 is
@@ -422,20 +430,20 @@ size_t rotate_hoisted_workspace_bytes(const fhe_ctx* c, u32 batch);
 constexpr u32 kRotSumMax = 16;
 int launch_rotate_sum_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* galois,
                               const u64* const* rot_b, const u64* const* rot_a,
-                              const u64* const* pt, u32 count, u32 batch, void* ws,
+                              const u64* const* pt, u32 level, u32 count, u32 batch, void* ws,
                               hipStream_t s);
 size_t rotate_sum_hoisted_workspace_bytes(const fhe_ctx* c, u32 batch);
 // sum_r rot_{galois[r]}(cts[r]) over different ciphertexts [batch][2][L][N] with one ModDown
 int launch_rotate_sum_multi(const fhe_ctx* c, u64* out, const u64* const* cts, const u32* galois,
-                            const u64* const* rot_b, const u64* const* rot_a, u32 count,
-                            u32 batch, void* ws, hipStream_t s);
+                            const u64* const* rot_b, const u64* const* rot_a, u32 level,
+                            u32 count, u32 batch, void* ws, hipStream_t s);
 size_t rotate_sum_multi_workspace_bytes(const fhe_ctx* c, u32 count, u32 batch);
 // out = sum_g rot_{giant[g]}(sum_b pt[g n1 + b] rot_{baby[b]}(in)), both hoistings
 int launch_linear_transform(const fhe_ctx* c, u64* out, const u64* in, u32 n1, u32 n2,
                             const u32* baby, const u64* const* baby_b, const u64* const* baby_a,
                             const u32* giant, const u64* const* giant_b,
-                            const u64* const* giant_a, const u64* const* pt, u32 batch, void* ws,
-                            hipStream_t s);
+                            const u64* const* giant_a, const u64* const* pt, u32 level,
+                            u32 batch, void* ws, hipStream_t s);
 size_t linear_transform_workspace_bytes(const fhe_ctx* c, u32 n2, u32 batch);
 
 // ---- launchers (pipeline.hip): SURVEY.md §8(f) row 4 -----------------------------------

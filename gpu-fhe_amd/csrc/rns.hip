@@ -452,8 +452,8 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
                            const u64* d2_own, const u64* evk_b, const u64* evk_a, u32 limb0,
                            u32 nlimbs, u32 batch, void* ws, hipStream_t s,
                            const KsEpilogue* epi, const KsHoist* hoist, u32 level) {
-  if (level && (level > c->L || limb0 != 0 || nlimbs != level || hoist)) {
-    set_error("keyswitch: a level call covers Q-limbs [0, level), level <= L, unhoisted");
+  if (level && (level > c->L || limb0 != 0 || nlimbs != level)) {
+    set_error("keyswitch: a level call covers Q-limbs [0, level), level <= L");
     return kInvalid;
   }
   if (c->K == 0) {
@@ -605,19 +605,28 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
   }
   if (npend && (rc = launch_modup_cols(c, pend, npend, s))) return rc;
   if (hoist_up) {
-    // the row-forward passes of every digit's extended rows: [0, lo) and [hi, rows), whose limbs
-    // are [limb0, limb0 + lo) and (the own Q-limbs past the digit, then P) [hi, L + K) when this
-    // is the single-device form (limb0 = 0, nlimbs = L)
-    for (u32 j = 0; j < c->dnum; ++j) {
-      const u32 lo = j * alpha, hi = std::min(L, lo + alpha);
+    // the row-forward passes of every live digit's extended rows: [0, lo) and [hi, rows), whose
+    // limbs are [0, lo) and (the live Q-limbs past the digit, then P) [hi, Lq) u [L, L + K) in the
+    // single-device form (limb0 = 0, nlimbs = Lq); at the top level the two ranges are one run
+    // [hi, L + K), below it the special rows' limb is L + (r - Lq) and they take a launch of their
+    // own
+    for (u32 j = 0; j < dl; ++j) {
+      const u32 lo = j * alpha, hi = std::min(Lq, lo + alpha);
       u64* e = ext + (u64)j * B * rn;
-      if (limb0 != 0 || nlimbs != L) {
-        set_error("keyswitch: the hoisted ModUp is single-device (all Q-limbs)");
+      if (limb0 != 0 || nlimbs != Lq) {
+        set_error("keyswitch: the hoisted ModUp is single-device (all live Q-limbs)");
         return kInvalid;
       }
-      if ((rc = launch_ntt_row_fwd_r2(c, e, rn, e, rn, batch, 0, lo, s)) ||
-          (rc = launch_ntt_row_fwd_r2(c, e + (u64)hi * n, rn, e + (u64)hi * n, rn, batch, hi,
-                                      rows - hi, s)))
+      if ((rc = launch_ntt_row_fwd_r2(c, e, rn, e, rn, batch, 0, lo, s))) return rc;
+      if (Lq == L) {
+        if ((rc = launch_ntt_row_fwd_r2(c, e + (u64)hi * n, rn, e + (u64)hi * n, rn, batch, hi,
+                                        rows - hi, s)))
+          return rc;
+        continue;
+      }
+      if ((rc = launch_ntt_row_fwd_r2(c, e + (u64)hi * n, rn, e + (u64)hi * n, rn, batch, hi,
+                                      Lq - hi, s)) ||
+          (rc = launch_ntt_row_fwd_r2(c, e + (u64)Lq * n, rn, e + (u64)Lq * n, rn, batch, L, K, s)))
         return rc;
     }
   }

@@ -379,10 +379,11 @@ class Context:
         return out
 
     def rotate_hoisted(self, ct, galois_elts, rot_keys, workspace=None, out=None):
-        """Several rotations of the same ct [..., 2, L, N] (NTT form) sharing one ModUp
-        (fhe_rotate_hoisted): galois_elts[r] with rot_keys[r] = (rot_b, rot_a), each
-        [dnum, L + K, N].  Returns [count, ..., 2, L, N]; output r decrypts to sigma_r(m)."""
-        _check_tensor(ct, "ct", (2, self.L, self.n))
+        """Several rotations of the same ct [..., 2, l, N] (NTT form, 1 <= l <= L: the level is
+        taken from the shape) sharing one ModUp (fhe_rotate_hoisted): galois_elts[r] with
+        rot_keys[r] = (rot_b, rot_a), each [dnum, L + K, N], the top-level key at every level.
+        Returns [count, ..., 2, l, N]; output r decrypts to sigma_r(m)."""
+        lv = self._ct_level(ct, "rotate_hoisted")
         elts = [int(g) for g in galois_elts]
         if len(rot_keys) != len(elts):
             raise ValueError("rotate_hoisted: one key per Galois element")
@@ -392,7 +393,7 @@ class Context:
             if kb.device != ct.device or ka.device != ct.device or not (
                     kb.is_contiguous() and ka.is_contiguous()):
                 raise ValueError("rotate_hoisted: keys must be contiguous on the ct's device")
-        batch = ct.numel() // (2 * self.L * self.n)
+        batch = ct.numel() // (2 * lv * self.n)
         count = len(elts)
         if out is None:
             out = _empty(count, *ct.shape, dtype=ct.dtype, device=ct.device)
@@ -405,17 +406,23 @@ class Context:
         b_arr = (ctypes.c_void_p * max(count, 1))(*[kb.data_ptr() for kb, _ in rot_keys])
         a_arr = (ctypes.c_void_p * max(count, 1))(*[ka.data_ptr() for _, ka in rot_keys])
         with torch.cuda.device(self.device):
-            check(lib.fhe_rotate_hoisted(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr, a_arr,
-                                         count, batch, _ptr(ws), _stream(ct)),
-                  "fhe_rotate_hoisted")
+            if lv == self.L:
+                check(lib.fhe_rotate_hoisted(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr, a_arr,
+                                             count, batch, _ptr(ws), _stream(ct)),
+                      "fhe_rotate_hoisted")
+            else:
+                check(lib.fhe_rotate_hoisted_level(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr,
+                                                   a_arr, lv, count, batch, _ptr(ws), _stream(ct)),
+                      "fhe_rotate_hoisted_level")
         return out
 
     def rotate_sum_hoisted(self, ct, galois_elts, rot_keys, pts, workspace=None, out=None):
-        """sum_r pts[r] * rot_{galois_elts[r]}(ct) for ct [..., 2, L, N] (NTT form) with one ModUp
-        and one ModDown (fhe_rotate_sum_hoisted, double hoisting): rot_keys[r] = (rot_b, rot_a)
-        [dnum, L + K, N], or None for the unrotated term (Galois element 1); pts[r] [L + K, N]
-        NTT form over Q u P.  Returns [..., 2, L, N]."""
-        _check_tensor(ct, "ct", (2, self.L, self.n))
+        """sum_r pts[r] * rot_{galois_elts[r]}(ct) for ct [..., 2, l, N] (NTT form, 1 <= l <= L:
+        the level is taken from the shape) with one ModUp and one ModDown (fhe_rotate_sum_hoisted,
+        double hoisting): rot_keys[r] = (rot_b, rot_a) [dnum, L + K, N], or None for the unrotated
+        term (Galois element 1); pts[r] [L + K, N] NTT form over Q u P.  Keys and plaintexts are
+        the top-level ones at every level, read in place.  Returns [..., 2, l, N]."""
+        lv = self._ct_level(ct, "rotate_sum_hoisted")
         elts = [int(g) for g in galois_elts]
         count = len(elts)
         if len(rot_keys) != count or len(pts) != count:
@@ -435,7 +442,7 @@ class Context:
             if kb.device != ct.device or ka.device != ct.device or not (
                     kb.is_contiguous() and ka.is_contiguous()):
                 raise ValueError("rotate_sum_hoisted: keys must be contiguous on the ct's device")
-        batch = ct.numel() // (2 * self.L * self.n)
+        batch = ct.numel() // (2 * lv * self.n)
         if out is None:
             out = _empty(*ct.shape, dtype=ct.dtype, device=ct.device)
         else:
@@ -449,10 +456,22 @@ class Context:
         a_arr = (ctypes.c_void_p * n_arr)(*[k[1].data_ptr() if k else None for k in rot_keys])
         p_arr = (ctypes.c_void_p * n_arr)(*[p.data_ptr() for p in pts])
         with torch.cuda.device(self.device):
-            check(lib.fhe_rotate_sum_hoisted(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr, a_arr,
-                                             p_arr, count, batch, _ptr(ws), _stream(ct)),
-                  "fhe_rotate_sum_hoisted")
+            if lv == self.L:
+                check(lib.fhe_rotate_sum_hoisted(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr,
+                                                 a_arr, p_arr, count, batch, _ptr(ws),
+                                                 _stream(ct)), "fhe_rotate_sum_hoisted")
+            else:
+                check(lib.fhe_rotate_sum_hoisted_level(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr,
+                                                       a_arr, p_arr, lv, count, batch, _ptr(ws),
+                                                       _stream(ct)), "fhe_rotate_sum_hoisted_level")
         return out
+
+    def _ct_level(self, ct, who):
+        """The level of a ciphertext [..., 2, l, N] of the hoisted rotations and rotation sums."""
+        _check_tensor(ct, "ct", (self.n,))
+        if ct.dim() < 3 or ct.shape[-3] != 2:
+            raise ValueError(f"{who}: ct must be [..., 2, l, N]")
+        return self._level(ct, f"{who}: ct")
 
     def _rot_keys(self, elts, rot_keys, ct, who):
         """Host arrays of key pointers (None for the unrotated element 1), shapes checked."""
@@ -483,13 +502,13 @@ class Context:
         return (ctypes.c_void_p * max(len(pts), 1))(*[p.data_ptr() for p in pts])
 
     def rotate_sum_multi(self, cts, galois_elts, rot_keys, workspace=None, out=None):
-        """sum_r rot_{galois_elts[r]}(cts[r]) over different ciphertexts (each [..., 2, L, N], NTT
-        form, one shape) with one ModDown (fhe_rotate_sum_multi, the giant-step sum of a BSGS
+        """sum_r rot_{galois_elts[r]}(cts[r]) over different ciphertexts (each [..., 2, l, N], NTT
+        form, one shape, 1 <= l <= L: the level is taken from it) with one ModDown (fhe_rotate_sum_multi, the giant-step sum of a BSGS
         linear transform); rot_keys[r] = (rot_b, rot_a) or None for Galois element 1."""
         if not cts:
             raise ValueError("rotate_sum_multi: at least one ciphertext")
         ct = cts[0]
-        _check_tensor(ct, "ct", (2, self.L, self.n))
+        lv = self._ct_level(ct, "rotate_sum_multi")
         for c in cts:
             if c.shape != ct.shape or c.device != ct.device or not c.is_contiguous():
                 raise ValueError("rotate_sum_multi: ciphertexts of one shape, contiguous, on one "
@@ -498,7 +517,7 @@ class Context:
         if len(cts) != len(elts):
             raise ValueError("rotate_sum_multi: one Galois element per ciphertext")
         g_arr, b_arr, a_arr = self._rot_keys(elts, rot_keys, ct, "rotate_sum_multi")
-        batch = ct.numel() // (2 * self.L * self.n)
+        batch = ct.numel() // (2 * lv * self.n)
         if out is None:
             out = _empty(*ct.shape, dtype=ct.dtype, device=ct.device)
         else:
@@ -508,17 +527,24 @@ class Context:
             lib.fhe_rotate_sum_multi_workspace(self._ptr, len(cts), batch))
         c_arr = (ctypes.c_void_p * len(cts))(*[c.data_ptr() for c in cts])
         with torch.cuda.device(self.device):
-            check(lib.fhe_rotate_sum_multi(self._ptr, _ptr(out), c_arr, g_arr, b_arr, a_arr,
-                                           len(elts), batch, _ptr(ws), _stream(ct)),
-                  "fhe_rotate_sum_multi")
+            if lv == self.L:
+                check(lib.fhe_rotate_sum_multi(self._ptr, _ptr(out), c_arr, g_arr, b_arr, a_arr,
+                                               len(elts), batch, _ptr(ws), _stream(ct)),
+                      "fhe_rotate_sum_multi")
+            else:
+                check(lib.fhe_rotate_sum_multi_level(self._ptr, _ptr(out), c_arr, g_arr, b_arr,
+                                                     a_arr, lv, len(elts), batch, _ptr(ws),
+                                                     _stream(ct)), "fhe_rotate_sum_multi_level")
         return out
 
     def linear_transform(self, ct, baby_elts, baby_keys, giant_elts, giant_keys, pts,
                          workspace=None, out=None):
         """Baby-step / giant-step plaintext-matrix product with both hoistings
         (fhe_linear_transform): sum_g rot_{giant[g]}(sum_b pts[g][b] rot_{baby[b]}(ct)) for
-        ct [..., 2, L, N] NTT form; pts[g][b] [L + K, N] NTT form over Q u P."""
-        _check_tensor(ct, "ct", (2, self.L, self.n))
+        ct [..., 2, l, N] NTT form (1 <= l <= L: the level is taken from the shape); pts[g][b]
+        [L + K, N] NTT form over Q u P and the keys [dnum, L + K, N], the top-level ones at every
+        level."""
+        lv = self._ct_level(ct, "linear_transform")
         baby = [int(g) for g in baby_elts]
         giant = [int(g) for g in giant_elts]
         n1, n2 = len(baby), len(giant)
@@ -527,7 +553,7 @@ class Context:
         bg, bb, ba = self._rot_keys(baby, baby_keys, ct, "linear_transform")
         gg, gb, ga = self._rot_keys(giant, giant_keys, ct, "linear_transform")
         p_arr = self._pts([p for row in pts for p in row], ct, "linear_transform")
-        batch = ct.numel() // (2 * self.L * self.n)
+        batch = ct.numel() // (2 * lv * self.n)
         if out is None:
             out = _empty(*ct.shape, dtype=ct.dtype, device=ct.device)
         else:
@@ -536,9 +562,14 @@ class Context:
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_linear_transform_workspace(self._ptr, n2, batch))
         with torch.cuda.device(self.device):
-            check(lib.fhe_linear_transform(self._ptr, _ptr(out), _ptr(ct), n1, n2, bg, bb, ba, gg,
-                                           gb, ga, p_arr, batch, _ptr(ws), _stream(ct)),
-                  "fhe_linear_transform")
+            if lv == self.L:
+                check(lib.fhe_linear_transform(self._ptr, _ptr(out), _ptr(ct), n1, n2, bg, bb, ba,
+                                               gg, gb, ga, p_arr, batch, _ptr(ws), _stream(ct)),
+                      "fhe_linear_transform")
+            else:
+                check(lib.fhe_linear_transform_level(self._ptr, _ptr(out), _ptr(ct), n1, n2, bg, bb,
+                                                     ba, gg, gb, ga, p_arr, lv, batch, _ptr(ws),
+                                                     _stream(ct)), "fhe_linear_transform_level")
         return out
 
     # ---- sampling, keys, encryption --------------------------------

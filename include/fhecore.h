@@ -179,9 +179,9 @@ int fhe_keyswitch_shard(const fhe_ctx* ctx, uint64_t* ks0, uint64_t* ks1, const 
  * fhe_rotate_workspace(ctx, pass) bytes are sufficient at every level (a level's regions are never
  * larger than the top level's); fhe_keyswitch_pass_batch governs the passes at every level.
  * Capture-safe like the top-level forms.
- * Top-level only (their current errors for fewer limbs): fhe_rotate_hoisted, the rotation sums,
- * fhe_linear_transform, and the multi-GPU (_shard, _dist, _loopback) forms.  There is no
- * level-switching plaintext multiply. */
+ * The hoisted rotations, the rotation sums and the linear transform have _level forms too (below,
+ * after their top-level forms).  Top-level only (their current errors for fewer limbs): the
+ * multi-GPU (_shard, _dist, _loopback) forms.  There is no level-switching plaintext multiply. */
 int fhe_keyswitch_level(const fhe_ctx* ctx, uint64_t* ks0, uint64_t* ks1, const uint64_t* d2,
                         const uint64_t* evk_b, const uint64_t* evk_a, uint32_t level,
                         uint32_t batch, void* workspace, fhe_stream_t stream);
@@ -378,6 +378,45 @@ int fhe_linear_transform(const fhe_ctx* ctx, uint64_t* out, const uint64_t* in, 
                          const uint64_t* const* giant_b, const uint64_t* const* giant_a,
                          const uint64_t* const* pt, uint32_t batch, void* workspace,
                          fhe_stream_t stream);
+
+/* ---- hoisted rotations, rotation sums and the linear transform over l <= L limbs -------------
+ * The four calls above with `level` = l live Q-limbs (1 <= l <= L), under the rule of the _level
+ * block further up: ciphertexts are [batch][2][l][N] (fhe_rotate_hoisted_level's out
+ * [count][batch][2][l][N]), the digits are D_j = [j alpha, min(l, (j + 1) alpha)) for
+ * j < ceil(l / alpha), and the rows run over {0 .. l-1} u {L .. L+K-1}.  The keys stay the
+ * caller's top-level keys [dnum][L + K][N] and the plaintext diagonals stay [L + K][N]; both are
+ * read in place at those rows (a diagonal is an integer polynomial whose residues do not depend
+ * on the level, so one encoding over Q u P serves every level, like a key).  Everything else is
+ * the top-level definition (oracle/pyoracle.py rotate_hoisted, rotate_sum_hoisted,
+ * rotate_sum_multi, linear_transform; restated for a level by tests/level_hoist_ref.py).
+ * level == L is bit-identical to the top-level forms, which are these calls with level = L.
+ * Errors: level == 0 or level > L returns FHE_EINVAL before any launch; every other error and
+ * aliasing rule is the top-level one with l in place of L.
+ * Workspace: fhe_rotate_hoisted_workspace(ctx, batch), fhe_rotate_sum_hoisted_workspace(ctx,
+ * batch), fhe_rotate_sum_multi_workspace(ctx, count, batch) and fhe_linear_transform_workspace(ctx,
+ * n2, batch) bytes, sized for L, are sufficient at every level (a level's regions are never
+ * larger than the top level's).  Capture-safe like the top-level forms: no allocation and no
+ * synchronisation with an explicit workspace. */
+int fhe_rotate_hoisted_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* in,
+                             const uint32_t* galois_elts, const uint64_t* const* rot_b,
+                             const uint64_t* const* rot_a, uint32_t level, uint32_t count,
+                             uint32_t batch, void* workspace, fhe_stream_t stream);
+int fhe_rotate_sum_hoisted_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* in,
+                                 const uint32_t* galois_elts, const uint64_t* const* rot_b,
+                                 const uint64_t* const* rot_a, const uint64_t* const* pt,
+                                 uint32_t level, uint32_t count, uint32_t batch, void* workspace,
+                                 fhe_stream_t stream);
+int fhe_rotate_sum_multi_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* const* cts,
+                               const uint32_t* galois_elts, const uint64_t* const* rot_b,
+                               const uint64_t* const* rot_a, uint32_t level, uint32_t count,
+                               uint32_t batch, void* workspace, fhe_stream_t stream);
+int fhe_linear_transform_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* in, uint32_t n1,
+                               uint32_t n2, const uint32_t* baby_elts,
+                               const uint64_t* const* baby_b, const uint64_t* const* baby_a,
+                               const uint32_t* giant_elts, const uint64_t* const* giant_b,
+                               const uint64_t* const* giant_a, const uint64_t* const* pt,
+                               uint32_t level, uint32_t batch, void* workspace,
+                               fhe_stream_t stream);
 
 /* ---- wire format (not in the reference) ------------------------------
  * A self-describing little-endian blob for any [polys][nlimbs][N] residue tensor over context

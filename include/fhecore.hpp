@@ -368,12 +368,14 @@ class Evaluator {
           "fhe_rotate_level");
     return out;
   }
-  // Several rotations of one ciphertext sharing a single ModUp (fhe_rotate_hoisted); output r
-  // decrypts to sigma_{galois_elts[r]}(m).
+  // Several rotations of one ciphertext (over l limbs, 1 <= l <= L, its level; top-level keys)
+  // sharing a single ModUp (fhe_rotate_hoisted_level); output r decrypts to
+  // sigma_{galois_elts[r]}(m).
   std::vector<Ciphertext> rotate_hoisted(const Ciphertext& ct, const std::vector<uint32_t>& galois_elts,
                                          const std::vector<const SwitchKey*>& keys) const {
-    if (ct.components != 2 || !ct.ntt_form || ct.limbs != ctx_.L())
-      throw Error(FHE_EINVAL, "rotate_hoisted: need a 2-component NTT-form ciphertext over L limbs");
+    if (ct.components != 2 || !ct.ntt_form || ct.limbs < 1 || ct.limbs > ctx_.L())
+      throw Error(FHE_EINVAL,
+                  "rotate_hoisted: need a 2-component NTT-form ciphertext over 1 .. L limbs");
     if (keys.size() != galois_elts.size())
       throw Error(FHE_EINVAL, "rotate_hoisted: one key per Galois element");
     const size_t words = (size_t)2 * ct.limbs * ctx_.n(), count = galois_elts.size();
@@ -385,9 +387,9 @@ class Evaluator {
     }
     const size_t need = fhe_rotate_hoisted_workspace(ctx_.get(), 1);
     if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
-    check(fhe_rotate_hoisted(ctx_.get(), all.data(), ct.data(), galois_elts.data(), kb.data(),
-                             ka.data(), (uint32_t)count, 1, ws_.data(), s_),
-          "fhe_rotate_hoisted");
+    check(fhe_rotate_hoisted_level(ctx_.get(), all.data(), ct.data(), galois_elts.data(), kb.data(),
+                                   ka.data(), ct.limbs, (uint32_t)count, 1, ws_.data(), s_),
+          "fhe_rotate_hoisted_level");
     std::vector<Ciphertext> out;
     for (size_t r = 0; r < count; ++r) {
       out.emplace_back(ctx_, 2, ct.limbs, true);
@@ -401,11 +403,12 @@ class Evaluator {
   // sum_r pts[r] * rot_{galois_elts[r]}(ct) with one ModUp and one ModDown (fhe_rotate_sum_hoisted,
   // double hoisting: the inner loop of a baby-step / giant-step linear transform).  keys[r] may be
   // null for galois_elts[r] == 1 (the unrotated term); pts[r] [L + K][N] NTT form over Q u P.
+  // ct spans l limbs (1 <= l <= L, its level); keys and plaintexts are the top-level ones.
   Ciphertext rotate_sum(const Ciphertext& ct, const std::vector<uint32_t>& galois_elts,
                         const std::vector<const SwitchKey*>& keys,
                         const std::vector<const DeviceBuffer*>& pts) const {
-    if (ct.components != 2 || !ct.ntt_form || ct.limbs != ctx_.L())
-      throw Error(FHE_EINVAL, "rotate_sum: need a 2-component NTT-form ciphertext over L limbs");
+    if (ct.components != 2 || !ct.ntt_form || ct.limbs < 1 || ct.limbs > ctx_.L())
+      throw Error(FHE_EINVAL, "rotate_sum: need a 2-component NTT-form ciphertext over 1 .. L limbs");
     const size_t count = galois_elts.size();
     if (keys.size() != count || pts.size() != count)
       throw Error(FHE_EINVAL, "rotate_sum: one key (or null) and one plaintext per term");
@@ -421,9 +424,10 @@ class Evaluator {
     Ciphertext out(ctx_, 2, ct.limbs, true);
     const size_t need = fhe_rotate_sum_hoisted_workspace(ctx_.get(), 1);
     if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
-    check(fhe_rotate_sum_hoisted(ctx_.get(), out.data(), ct.data(), galois_elts.data(), kb.data(),
-                                 ka.data(), pp.data(), (uint32_t)count, 1, ws_.data(), s_),
-          "fhe_rotate_sum_hoisted");
+    check(fhe_rotate_sum_hoisted_level(ctx_.get(), out.data(), ct.data(), galois_elts.data(),
+                                       kb.data(), ka.data(), pp.data(), ct.limbs, (uint32_t)count, 1,
+                                       ws_.data(), s_),
+          "fhe_rotate_sum_hoisted_level");
     return out;
   }
 
