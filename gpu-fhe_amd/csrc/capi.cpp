@@ -617,4 +617,97 @@ int fhe_mul_relin_level(const fhe_ctx* c, uint64_t* out, const uint64_t* a, cons
   return launch_mul_relin(c, out, a, b, evk_b, evk_a, level, batch, rescale != 0, ws, hs(s));
 }
 
+size_t fhe_lincomb_workspace(const fhe_ctx* c, uint32_t batch) {
+  return c ? lincomb_workspace_bytes(c, batch) : 0;
+}
+
+// out [batch][2][out_level][N] against one input of in_words words: the input itself, in place
+// (same start, same stride, no rescale), or disjoint from it
+static int check_plain_alias(const uint64_t* out, uint64_t out_words, const uint64_t* in,
+                             uint64_t in_words, bool in_place_ok, const std::string& what) {
+  if (in_place_ok && out == in && out_words == in_words) return kOk;
+  if (spans_overlap(out, out_words, in, in_words)) {
+    set_error(what + " (out is either that input itself -- same start, same level, no rescale "
+                     "-- or disjoint from it)");
+    return kInvalid;
+  }
+  return kOk;
+}
+
+int fhe_lincomb_level(const fhe_ctx* c, uint64_t* out, const uint64_t* const* cts,
+                      const uint32_t* in_levels, const uint64_t* scalars, uint32_t scalar_stride,
+                      int has_const, uint32_t level, uint32_t count, uint32_t batch, int rescale,
+                      void* ws, fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_lincomb_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_lincomb_level"))) return rc;
+  if (count == 0 || count > kLincombMax) {
+    set_error("fhe_lincomb_level: count must be 1..16");
+    return kInvalid;
+  }
+  if (rescale && level < 2) {
+    set_error("fhe_lincomb_level: rescale needs level >= 2");
+    return kInvalid;
+  }
+  if (scalar_stride < level) {
+    set_error("fhe_lincomb_level: scalar_stride must be at least level");
+    return kInvalid;
+  }
+  if (!out || !cts || !in_levels || !scalars) {
+    set_error("fhe_lincomb_level: null output, ciphertext array, level array or scalar table");
+    return kInvalid;
+  }
+  const uint64_t out_words = (uint64_t)batch * 2 * (level - (rescale ? 1 : 0)) * c->n;
+  for (uint32_t t = 0; t < count; ++t) {
+    if (!cts[t]) {
+      set_error("fhe_lincomb_level: null ciphertext pointer for term " + std::to_string(t));
+      return kInvalid;
+    }
+    if (in_levels[t] < level || in_levels[t] > c->L) {
+      set_error("fhe_lincomb_level: in_levels[" + std::to_string(t) + "] must be in [level, L]");
+      return kInvalid;
+    }
+    if ((rc = check_plain_alias(out, out_words, cts[t], (uint64_t)batch * 2 * in_levels[t] * c->n,
+                                !rescale, "fhe_lincomb_level: out overlaps term " +
+                                              std::to_string(t))))
+      return rc;
+  }
+  if (batch == 0) return kOk;
+  if (rescale && (rc = ensure_ws(c, lincomb_workspace_bytes(c, batch), &ws, hs(s)))) return rc;
+  return launch_lincomb(c, out, cts, in_levels, scalars, scalar_stride, has_const != 0, level,
+                        count, batch, rescale != 0, ws, hs(s));
+}
+
+int fhe_mul_plain_level(const fhe_ctx* c, uint64_t* out, const uint64_t* ct, const uint64_t* pt,
+                        uint32_t pt_rows, uint32_t pt_batch, uint32_t level, uint32_t batch,
+                        int rescale, void* ws, fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_mul_plain_level");
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_mul_plain_level"))) return rc;
+  if (rescale && level < 2) {
+    set_error("fhe_mul_plain_level: rescale needs level >= 2");
+    return kInvalid;
+  }
+  if (pt_rows < level) {
+    set_error("fhe_mul_plain_level: pt_rows must be at least level");
+    return kInvalid;
+  }
+  if (pt_batch != 1 && pt_batch != batch) {
+    set_error("fhe_mul_plain_level: pt_batch must be 1 or batch");
+    return kInvalid;
+  }
+  if (!out || !ct || !pt) {
+    set_error("fhe_mul_plain_level: null data pointer");
+    return kInvalid;
+  }
+  const uint64_t ct_words = (uint64_t)batch * 2 * level * c->n;
+  const uint64_t out_words = (uint64_t)batch * 2 * (level - (rescale ? 1 : 0)) * c->n;
+  if ((rc = check_plain_alias(out, out_words, ct, ct_words, !rescale,
+                              "fhe_mul_plain_level: out overlaps ct")) ||
+      (rc = check_plain_alias(out, out_words, pt, (uint64_t)pt_batch * pt_rows * c->n, false,
+                              "fhe_mul_plain_level: out overlaps pt")))
+    return rc;
+  if (batch == 0) return kOk;
+  if (rescale && (rc = ensure_ws(c, lincomb_workspace_bytes(c, batch), &ws, hs(s)))) return rc;
+  return launch_mul_plain(c, out, ct, pt, pt_rows, pt_batch, level, batch, rescale != 0, ws, hs(s));
+}
+
 }  // extern "C"

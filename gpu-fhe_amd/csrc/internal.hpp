@@ -300,6 +300,22 @@ int launch_vec_mod(int op, u64* out, const u64* a, const u64* b, u64 rows, u64 c
                    const ModParams* d_mods, const ModArgs& inl, u64 mod_stride, int signed_in,
                    hipStream_t s);
 
+// ---- launchers (plain.hip) -------------------------------------------------------------
+// out = [rescale]( sum_{t < count} scalars[t][l] cts[t] (+ scalars[count][l] on c0) ) over the first
+// `level` limbs: cts[t] [batch][2][in_levels[t]][N] NTT form (level <= in_levels[t] <= L; host
+// arrays), scalars a device table [count + 1][scalar_stride] of canonical residues.  out
+// [batch][2][level][N], or with rescale [batch][2][level - 1][N] through ws
+// (lincomb_workspace_bytes: the sum, then launch_rescale's regions).  Arguments checked by capi.cpp.
+constexpr u32 kLincombMax = 16;
+int launch_lincomb(const fhe_ctx* c, u64* out, const u64* const* cts, const u32* in_levels,
+                   const u64* scalars, u32 scalar_stride, bool has_const, u32 level, u32 count,
+                   u32 batch, bool rescale, void* ws, hipStream_t s);
+// out = [rescale]( ct * pt ): ct [batch][2][level][N], pt [pt_batch][pt_rows][N] (rows 0 .. level-1
+// read in place; pt_batch 1 or batch)
+int launch_mul_plain(const fhe_ctx* c, u64* out, const u64* ct, const u64* pt, u32 pt_rows,
+                     u32 pt_batch, u32 level, u32 batch, bool rescale, void* ws, hipStream_t s);
+size_t lincomb_workspace_bytes(const fhe_ctx* c, u32 batch);
+
 // ---- launchers (rns.hip) --------------------------------------------------------------
 // Per-rank body of the hybrid key-switch (SURVEY.md §8a', §8e) over `batch` ciphertexts sharing
 // one key: c_all [batch][L][N] coefficient form of the whole d2 (all-gathered), d2_own

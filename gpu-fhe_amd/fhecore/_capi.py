@@ -99,6 +99,10 @@ SIGNATURES = {
                                ctypes.POINTER(_u32), ctypes.POINTER(_i32), _vp]),
     "fhe_mul_relin_workspace": (_sz, [_vp, _u32]),
     "fhe_mul_relin": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _vp, _vp]),
+    "fhe_lincomb_workspace": (_sz, [_vp, _u32]),
+    "fhe_lincomb_level": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _i32, _u32, _u32, _u32, _i32, _vp,
+                                 _vp]),
+    "fhe_mul_plain_level": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _vp, _vp]),
     "fhe_graph_begin": (_i32, [_vp]),
     "fhe_graph_end": (_i32, [_vp, ctypes.POINTER(_vp)]),
     "fhe_graph_launch": (_i32, [_vp, _vp]),

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes
 import secrets
 import threading
+from fractions import Fraction
 from functools import lru_cache
 
 import numpy as np
@@ -685,6 +686,90 @@ class Context:
                                               _ptr(evk_a), lv, batch, int(rescale), _ptr(ws),
                                               _stream(a)), "fhe_mul_relin_level")
         return out
+
+    # ---- plaintext arithmetic at any level (fhe_lincomb_level / fhe_mul_plain_level) --------
+    def encode_scalars(self, values, delta=1.0, exact: bool = False):
+        """Device table [len(values), L] of round(v * delta) mod q_j (Python integers, negative
+        values wrap): the `scalars` of lincomb, one row per term, encoded once over all L limbs
+        and read at every level.  exact=True: the values are already integers."""
+        if exact:
+            ints = [int(v) for v in values]
+        else:
+            d = Fraction(delta)
+            ints = [int(round(Fraction(v) * d)) for v in values]
+        tab = np.array([[k % q for q in self.moduli] for k in ints], dtype=np.uint64)
+        return to_device(tab.reshape(len(ints), self.L), self._dev())
+
+    def lincomb(self, cts, scalars, const: bool = False, rescale: bool = False, level=None,
+                workspace=None, out=None):
+        """[rescale]( sum_i scalars[i] * cts[i] (+ scalars[len(cts)] on every slot of c0) ) in one
+        pass (fhe_lincomb_level).  cts[i] [..., 2, l_i, N] NTT form with one leading (batch) shape
+        and any levels l_i >= level (default: the lowest of them): a higher term is cut to `level`
+        limbs on the fly.  scalars: a device table [rows >= len(cts) (+ 1 with const), >= level]
+        (encode_scalars).  Returns [..., 2, level, N], or with rescale [..., 2, level - 1, N].
+        out may be one of the cts at that level when rescale is off.  workspace (rescale only):
+        fhe_lincomb_workspace(ctx, batch) bytes; None takes the context's internal one, which is
+        refused while a Graph is capturing."""
+        if not cts:
+            raise ValueError("lincomb: at least one ciphertext")
+        lvs = [self._ct_level(c, "lincomb") for c in cts]
+        ref = cts[0]
+        lead = tuple(ref.shape[:-3])
+        for c in cts:
+            if tuple(c.shape[:-3]) != lead or c.device != ref.device:
+                raise ValueError("lincomb: ciphertexts of one batch shape on one device")
+        level = min(lvs) if level is None else int(level)
+        count = len(cts)
+        _check_tensor(scalars, "lincomb: scalars")
+        if scalars.dim() != 2 or scalars.shape[0] < count + (1 if const else 0) or \
+                scalars.device != ref.device:
+            raise ValueError("lincomb: scalars must be a device table [len(cts) (+ 1), stride]")
+        batch = ref.numel() // (2 * lvs[0] * self.n)
+        shape = (*lead, 2, level - (1 if rescale else 0), self.n)
+        if out is None:
+            out = _empty(shape, dtype=ref.dtype, device=ref.device)
+        else:
+            _check_out(out, ref, shape, "lincomb: out")
+        c_arr = (ctypes.c_void_p * count)(*[c.data_ptr() for c in cts])
+        l_arr = (ctypes.c_uint32 * count)(*lvs)
+        with torch.cuda.device(self.device):
+            check(load().fhe_lincomb_level(self._ptr, _ptr(out), c_arr, l_arr, _ptr(scalars),
+                                           scalars.shape[1], int(const), level, count, batch,
+                                           int(rescale), _ptr(workspace), _stream(ref)),
+                  "fhe_lincomb_level")
+        return out
+
+    def mul_plain(self, ct, pt, rescale: bool = False, workspace=None, out=None):
+        """[rescale]( ct * pt ) (fhe_mul_plain_level): ct [..., 2, l, N] NTT form, pt [rows, N]
+        (one plaintext for the whole batch) or [..., rows, N] (one per ciphertext), NTT form,
+        rows >= l: a top-level [L, N] plaintext or a diagonal [L + K, N] is read in place at every
+        level.  out may be ct when rescale is off; workspace as lincomb."""
+        lv = self._ct_level(ct, "mul_plain")
+        _check_tensor(pt, "mul_plain: pt", (self.n,))
+        lead = tuple(ct.shape[:-3])
+        if pt.dim() < 2 or pt.device != ct.device or (
+                pt.dim() > 2 and tuple(pt.shape[:-2]) != lead):
+            raise ValueError("mul_plain: pt must be [rows, N] or [..., rows, N] with ct's batch "
+                             "shape, on ct's device")
+        batch = ct.numel() // (2 * lv * self.n)
+        shape = (*lead, 2, lv - (1 if rescale else 0), self.n)
+        if out is None:
+            out = _empty(shape, dtype=ct.dtype, device=ct.device)
+        else:
+            _check_out(out, ct, shape, "mul_plain: out")
+        with torch.cuda.device(self.device):
+            check(load().fhe_mul_plain_level(self._ptr, _ptr(out), _ptr(ct), _ptr(pt),
+                                             pt.shape[-2], 1 if pt.dim() == 2 else batch, lv,
+                                             batch, int(rescale), _ptr(workspace), _stream(ct)),
+                  "fhe_mul_plain_level")
+        return out
+
+    def drop_level(self, ct, level: int, out=None):
+        """ct [..., 2, l, N] -> its first `level` <= l limbs [..., 2, level, N] (dropping RNS limbs
+        lowers the level; the scale is unchanged): lincomb with one term and scalar 1."""
+        if getattr(self, "_one", None) is None:
+            self._one = self.encode_scalars([1], exact=True)
+        return self.lincomb([ct], self._one, level=level, out=out)
 
     # ---- SURVEY.md §8(f) row 2: wire format ----------------------------------------------
     def serialize(self, x, ntt_form: bool, limb0: int = 0) -> bytes:

@@ -180,8 +180,10 @@ int fhe_keyswitch_shard(const fhe_ctx* ctx, uint64_t* ks0, uint64_t* ks1, const 
  * larger than the top level's); fhe_keyswitch_pass_batch governs the passes at every level.
  * Capture-safe like the top-level forms.
  * The hoisted rotations, the rotation sums and the linear transform have _level forms too (below,
- * after their top-level forms).  Top-level only (their current errors for fewer limbs): the
- * multi-GPU (_shard, _dist, _loopback) forms.  There is no level-switching plaintext multiply. */
+ * after their top-level forms), and the plaintext arithmetic (linear combination with scalars,
+ * plaintext multiply, level drop) is fhe_lincomb_level / fhe_mul_plain_level further
+ * down. Top-level only (their current errors for fewer limbs): the multi-GPU (_shard, _dist,
+ * _loopback) forms. */
 int fhe_keyswitch_level(const fhe_ctx* ctx, uint64_t* ks0, uint64_t* ks1, const uint64_t* d2,
                         const uint64_t* evk_b, const uint64_t* evk_a, uint32_t level,
                         uint32_t batch, void* workspace, fhe_stream_t stream);
@@ -471,6 +473,48 @@ size_t fhe_mul_relin_workspace(const fhe_ctx* ctx, uint32_t batch);
 int fhe_mul_relin(const fhe_ctx* ctx, uint64_t* out, const uint64_t* a, const uint64_t* b,
                   const uint64_t* evk_b, const uint64_t* evk_a, uint32_t batch, int rescale,
                   void* workspace, fhe_stream_t stream);
+
+/* ---- plaintext arithmetic over l <= L limbs: scalars, constants, plaintexts, level drop --------
+ * The leaves of a polynomial evaluation (CKKS bootstrapping's EvalMod) in one pass each, under the
+ * rule of the _level block further up: `level` = l live Q-limbs, 1 <= l <= L, NTT form, canonical
+ * residues in and out.
+ * fhe_lincomb_level:
+ *   out = [rescale]( sum_{i < count} k_i * cts[i]|_l  (+ k_count on every slot of c0) ),
+ * count in 1..16.  cts[i] is [batch][2][in_levels[i]][N] with l <= in_levels[i] <= L (cts and
+ * in_levels are host arrays); only its limbs 0 .. l-1 are read, through its own stride: dropping
+ * RNS limbs IS the level drop, so one term with k = 1 is the strided copy [batch][2][l_in][N] ->
+ * [batch][2][l][N], and ciphertexts of different levels add at the lowest one.  `scalars` is a
+ * DEVICE table [count + 1][scalar_stride] of canonical residues, row i column j = k_i mod q_j
+ * (columns j < l are read; scalar_stride >= l, so one table encoded over all L limbs serves every
+ * level, like a key).  Row `count` is the additive constant, read only when has_const != 0: a
+ * constant polynomial has the same value at every NTT slot, so it is added to every element of c0
+ * and to nothing of c1.  out is [batch][2][l][N]; with rescale != 0 (l >= 2) it is
+ * [batch][2][l-1][N], defined as -- and bit-identical to -- the canonical sum followed by
+ * fhe_rescale(..., nlimbs = l, ntt_form = 1).
+ * fhe_mul_plain_level: out = [rescale]( ct * pt ) for ct [batch][2][l][N] and a plaintext pt
+ * [pt_batch][pt_rows][N], NTT form, pt_rows >= l, rows 0 .. l-1 read in place (a top-level [L][N]
+ * plaintext or a BSGS diagonal [L + K][N] serves every level; an [l][N] one is accepted too);
+ * pt_batch is 1 (one plaintext for the whole batch) or batch.  Bit-identical to fhe_vec_mul on both
+ * components followed, with rescale, by fhe_rescale(ntt_form = 1).
+ * Errors (FHE_EINVAL before any launch): level == 0 or level > L; in_levels[i] < level or > L;
+ * count == 0 or count > 16; scalar_stride < level; pt_rows < level; pt_batch not 1 or batch; a null
+ * pointer (also inside cts); rescale with level < 2.
+ * Aliasing: without rescale, out may be an input ciphertext itself (same start pointer, and for
+ * fhe_lincomb_level in_levels[i] == level); any other overlap of out with an input ciphertext or
+ * the plaintext, and any overlap at all with rescale, is FHE_EINVAL.  The scalar table and the
+ * workspace must not overlap out (not checked).
+ * Workspace: only the rescaling forms take one, fhe_lincomb_workspace(ctx, batch) bytes for both
+ * calls, sized for L and sufficient at every level; NULL = internal (FHE_EINVAL while the stream is
+ * capturing).  Capture-safe: no scalar travels in the kernel arguments, nothing is allocated or
+ * synchronised with an explicit workspace. */
+size_t fhe_lincomb_workspace(const fhe_ctx* ctx, uint32_t batch);
+int fhe_lincomb_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* const* cts,
+                      const uint32_t* in_levels, const uint64_t* scalars, uint32_t scalar_stride,
+                      int has_const, uint32_t level, uint32_t count, uint32_t batch, int rescale,
+                      void* workspace, fhe_stream_t stream);
+int fhe_mul_plain_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* ct, const uint64_t* pt,
+                        uint32_t pt_rows, uint32_t pt_batch, uint32_t level, uint32_t batch,
+                        int rescale, void* workspace, fhe_stream_t stream);
 
 /* ---- HIP graphs: capture a sequence of libfhecore calls on `stream` and replay it -----------
  * Between fhe_graph_begin and fhe_graph_end every call that takes a workspace must be given an

@@ -430,8 +430,61 @@ class Evaluator {
           "fhe_rotate_sum_hoisted_level");
     return out;
   }
+  // [rescale]( sum_i scalars[i] * cts[i] (+ scalars[count] on every slot of c0) ) at `level`
+  // (fhe_lincomb_level; level 0: the lowest of the inputs' levels).  cts[i]: 2-component NTT-form
+  // ciphertexts over l_i >= level limbs, cut to `level` limbs on the fly.  scalars: a device table
+  // [count + 1][stride] of residues k_i mod q_j, stride >= level (row count read with has_const).
+  Ciphertext lincomb(const std::vector<const Ciphertext*>& cts, const DeviceBuffer& scalars,
+                     uint32_t stride, bool has_const, bool rescale, uint32_t level = 0) const {
+    const size_t count = cts.size();
+    std::vector<const uint64_t*> p(count ? count : 1);
+    std::vector<uint32_t> lv(count ? count : 1);
+    uint32_t lo = ctx_.L();
+    for (size_t i = 0; i < count; ++i) {
+      if (!cts[i] || cts[i]->components != 2 || !cts[i]->ntt_form)
+        throw Error(FHE_EINVAL, "lincomb: need 2-component NTT-form ciphertexts");
+      p[i] = cts[i]->data();
+      lv[i] = cts[i]->limbs;
+      lo = lv[i] < lo ? lv[i] : lo;
+    }
+    if (level == 0) level = lo;
+    if (!stride || scalars.size() < (count + (has_const ? 1 : 0)) * (size_t)stride)
+      throw Error(FHE_EINVAL, "lincomb: the scalar table holds count (+ 1) rows of `stride` words");
+    if (rescale && level < 2) throw Error(FHE_EINVAL, "lincomb: rescale needs level >= 2");
+    Ciphertext out(ctx_, 2, level - (rescale ? 1 : 0), true);
+    check(fhe_lincomb_level(ctx_.get(), out.data(), p.data(), lv.data(), scalars.data(), stride,
+                            has_const ? 1 : 0, level, (uint32_t)count, 1, rescale ? 1 : 0,
+                            rescale ? plain_ws() : nullptr, s_),
+          "fhe_lincomb_level");
+    return out;
+  }
+  // [rescale]( ct * pt ) (fhe_mul_plain_level): pt a 1-component NTT-form plaintext over at least
+  // ct's limbs (a top-level [L][N] plaintext or a diagonal [L + K][N] serves every level).
+  Ciphertext mul_plain(const Ciphertext& ct, const Ciphertext& pt, bool rescale) const {
+    if (ct.components != 2 || !ct.ntt_form || pt.components != 1 || !pt.ntt_form)
+      throw Error(FHE_EINVAL, "mul_plain: need an NTT-form ciphertext and a 1-component plaintext");
+    if (rescale && ct.limbs < 2) throw Error(FHE_EINVAL, "mul_plain: rescale needs level >= 2");
+    Ciphertext out(ctx_, 2, ct.limbs - (rescale ? 1 : 0), true);
+    check(fhe_mul_plain_level(ctx_.get(), out.data(), ct.data(), pt.data(), pt.limbs, 1, ct.limbs,
+                              1, rescale ? 1 : 0, rescale ? plain_ws() : nullptr, s_),
+          "fhe_mul_plain_level");
+    return out;
+  }
+  // The first `level` limbs of ct: lincomb with one term and scalar 1.
+  Ciphertext drop_level(const Ciphertext& ct, uint32_t level) const {
+    if (ones_.size() != ctx_.L()) {
+      ones_ = DeviceBuffer(ctx_.L());
+      ones_.upload(std::vector<uint64_t>(ctx_.L(), 1));
+    }
+    return lincomb({&ct}, ones_, ctx_.L(), false, false, level);
+  }
 
  private:
+  uint64_t* plain_ws() const {
+    const size_t need = fhe_lincomb_workspace(ctx_.get(), 1);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    return ws_.data();
+  }
   static void same(const Ciphertext& a, const Ciphertext& b, const char* who) {
     if (a.components != b.components || a.limbs != b.limbs || a.n != b.n)
       throw Error(FHE_EINVAL, std::string(who) + ": shape mismatch");
@@ -439,6 +492,7 @@ class Evaluator {
   const Context& ctx_;
   hipStream_t s_;
   mutable DeviceBuffer ws_;
+  mutable DeviceBuffer ones_;  // drop_level's scalar table: 1 mod q_j
 };
 
 }  // namespace fhe
