@@ -3,6 +3,7 @@
 #include "../../include/fhecore.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <string>
 
 #include "internal.hpp"
@@ -708,6 +709,38 @@ int fhe_mul_plain_level(const fhe_ctx* c, uint64_t* out, const uint64_t* ct, con
   if (batch == 0) return kOk;
   if (rescale && (rc = ensure_ws(c, lincomb_workspace_bytes(c, batch), &ws, hs(s)))) return rc;
   return launch_mul_plain(c, out, ct, pt, pt_rows, pt_batch, level, batch, rescale != 0, ws, hs(s));
+}
+
+size_t fhe_mod_raise_workspace(const fhe_ctx* c, uint32_t batch) {
+  return c ? mod_raise_workspace_bytes(c, batch) : 0;
+}
+
+int fhe_mod_raise(const fhe_ctx* c, uint64_t* out, const uint64_t* in, uint32_t in_level,
+                  uint32_t out_level, uint32_t batch, void* ws, fhe_stream_t s) {
+  if (!c) {
+    set_error("fhe_mod_raise: null context");
+    return kInvalid;
+  }
+  if (in_level == 0 || in_level > c->L || out_level == 0 || out_level > c->L) {
+    set_error("fhe_mod_raise: in_level and out_level must be in [1, L]");
+    return kInvalid;
+  }
+  if (!out || !in) {
+    set_error("fhe_mod_raise: null data pointer");
+    return kInvalid;
+  }
+  if (spans_overlap(out, (uint64_t)batch * 2 * out_level * c->n, in,
+                    (uint64_t)batch * 2 * in_level * c->n)) {
+    set_error("fhe_mod_raise: out overlaps in");
+    return kInvalid;
+  }
+  if (batch == 0) return kOk;
+  int rc = ensure_ws(c, mod_raise_workspace_bytes(c, batch), &ws, hs(s));
+  if (rc) return rc;
+  // FHECORE_MODRAISE_UNFUSED=1: the separate-spread form of wide contexts on any context (the
+  // same bits; tools/modraise_times.py times the two against each other)
+  const char* u = std::getenv("FHECORE_MODRAISE_UNFUSED");
+  return launch_mod_raise(c, out, in, in_level, out_level, batch, ws, u && u[0] == '1', hs(s));
 }
 
 }  // extern "C"

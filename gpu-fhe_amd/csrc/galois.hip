@@ -103,6 +103,23 @@ __global__ __launch_bounds__(kThreads) void k_rescale_finish(u64* __restrict__ o
   out[(p * (nl - 1) + i) * n + c] = csub(shoup_lazy(d, w.x, w.y, q), q);
 }
 
+// ModRaise, the unfused form (wide contexts): x0 [polys][N] (coefficient form of limb 0) ->
+// limbs i = 1 .. nl-1 of out [polys][nl][N] = ((x0 + h) mod q_0 - h) mod q_i, h = q_0 / 2 (to be
+// NTT'd in place).  Grid y = i - 1.
+__global__ __launch_bounds__(kThreads) void k_modraise_spread(u64* __restrict__ out,
+                                                              const u64* __restrict__ x0, u32 nl,
+                                                              u32 log_n,
+                                                              const ModParams* __restrict__ mods) {
+  const u64 n = 1ull << log_n;
+  const u64 c = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 i = blockIdx.y + 1;
+  const u64 p = blockIdx.z;
+  const ModParams m0 = mods[0], mi = mods[i];
+  const u64 h = m0.q >> 1;
+  const u64 t = csub(x0[p * n + c] + h, m0.q);
+  out[(p * nl + i) * n + c] = csub(reduce_word(t, mi) + mi.q - reduce_word(h, mi), mi.q);
+}
+
 inline u64 modinv_u64(u64 a, u64 q) { return powmod_u64(a % q, q - 2, q); }
 
 // k^-1 mod 2^bits for odd k (Newton: each step doubles the correct low bits)
@@ -377,6 +394,46 @@ int launch_rescale(const fhe_ctx* c, u64* out, const u64* in, u32 polys, u32 nl,
   if ((rc = launch_ntt(c, true, tmp, tmp, polys, (u64)(nl - 1) * n, 0, nl - 1, s))) return rc;
   k_rescale_finish<<<g, kThreads, 0, s>>>(out, in, tmp, nl, c->log_n, tab, c->d_mods);
   FHE_HIP_CHECK(hipGetLastError());
+  return kOk;
+}
+
+size_t mod_raise_workspace_bytes(const fhe_ctx* c, u32 batch) {
+  return (size_t)2 * batch * c->n * sizeof(u64);
+}
+
+int launch_mod_raise(const fhe_ctx* c, u64* out, const u64* in, u32 in_level, u32 out_level,
+                     u32 batch, void* ws, bool unfused, hipStream_t s) {
+  if (in_level == 0 || in_level > c->L || out_level == 0 || out_level > c->L) {
+    set_error("mod_raise: levels must be in [1, L]");
+    return kInvalid;
+  }
+  if (batch == 0) return kOk;
+  const u64 n = c->n;
+  const u32 polys = 2 * batch;
+  const u64 in_ps = (u64)in_level * n, out_ps = (u64)out_level * n;
+  int rc;
+  if (out_level > 1) {
+    // INTT of limb 0, lift it into limbs 1 .. out_level-1, NTT those
+    u64* x0 = static_cast<u64*>(ws);  // [polys][N]
+    if ((rc = launch_ntt_strided(c, false, in, in_ps, x0, n, polys, 0, 1, s))) return rc;
+    if (!c->wide && !unfused) {
+      // the lift rides on the column-forward pass (k_modraise_col); the row pass runs in place
+      if ((rc = launch_modraise_col(c, x0, out, polys, out_level, s))) return rc;
+      if ((rc = launch_ntt_row_fwd_r2(c, out + n, out_ps, out + n, out_ps, polys, 1, out_level - 1,
+                                      s)))
+        return rc;
+    } else {
+      if ((rc = check_grid(n / kThreads, kThreads, out_level - 1, polys, "mod_raise"))) return rc;
+      const dim3 g((u32)(n / kThreads), out_level - 1, polys);
+      k_modraise_spread<<<g, kThreads, 0, s>>>(out, x0, out_level, c->log_n, c->d_mods);
+      FHE_HIP_CHECK(hipGetLastError());
+      if ((rc = launch_ntt(c, true, out + n, out + n, polys, out_ps, 1, out_level - 1, s)))
+        return rc;
+    }
+  }
+  // limb 0 is the input's, bit for bit
+  FHE_HIP_CHECK(hipMemcpy2DAsync(out, out_ps * sizeof(u64), in, in_ps * sizeof(u64), n * sizeof(u64),
+                                 polys, hipMemcpyDeviceToDevice, s));
   return kOk;
 }
 

@@ -281,6 +281,11 @@ int launch_moddown_row(const fhe_ctx* c, const ModDownRowArgs& a, hipStream_t s)
 // (coefficient form of limb nq) -> dst [polys][nq][N] column-passed; half = rescale half table.
 int launch_rescale_col(const fhe_ctx* c, const u64* last, u64* dst, u32 polys, u32 nq,
                        const u64* half, hipStream_t s);
+// ModRaise, lift + column-forward pass in one (ntt.hip, k_modraise_col): x [polys][N] (coefficient
+// form of limb 0) -> limbs 1 .. out_level-1 of dst [polys][out_level][N] column-passed (schedule
+// from 2: launch_ntt_row_fwd_r2 finishes them); limb 0 of dst is not touched.
+int launch_modraise_col(const fhe_ctx* c, const u64* x, u64* dst, u32 polys, u32 out_level,
+                        hipStream_t s);
 // Fused ct x ct tensor: a, b [batch][2][nlimbs][N] coefficient form -> d [batch][3][nlimbs][N].
 int launch_hommult(const fhe_ctx* c, u64* d, const u64* a, const u64* b, u32 batch, u32 limb0,
                    u32 nlimbs, void* ws, hipStream_t s);
@@ -425,6 +430,12 @@ int launch_automorphism(const fhe_ctx* c, u64* out, u64 pout, const u64* in, u64
 int launch_rescale(const fhe_ctx* c, u64* out, const u64* in, u32 polys, u32 nl, bool ntt,
                    void* ws, hipStream_t s);
 size_t rescale_workspace_bytes(const fhe_ctx* c, u32 polys, u32 nl);
+// ModRaise: in [batch][2][in_level][N] NTT form (limb 0 read) -> out [batch][2][out_level][N], the
+// centred lift of INTT_0(in[p][0]) reduced mod q_l, NTT form; ws [2 batch][N].  unfused: the
+// separate-spread form of wide contexts on any context (tools/modraise_times.py measures it).
+int launch_mod_raise(const fhe_ctx* c, u64* out, const u64* in, u32 in_level, u32 out_level,
+                     u32 batch, void* ws, bool unfused, hipStream_t s);
+size_t mod_raise_workspace_bytes(const fhe_ctx* c, u32 batch);
 // in/out [batch][2][L][N] NTT form; rot_b/rot_a [dnum][L + K][N] (key for sigma_k(s) -> s)
 // (level: the Q-limbs of in / out, 1 .. L; the keys stay the top-level ones)
 int launch_rotate(const fhe_ctx* c, u64* out, const u64* in, u32 galois_elt, const u64* rot_b,

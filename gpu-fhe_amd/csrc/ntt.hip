@@ -2148,6 +2148,66 @@ int rescale_col_dispatch(const fhe_ctx* c, const u64* last, u64* dst, u32 polys,
                                                             c->d_tw_fwd, c->d_mods);
   return kOk;
 }
+
+// ModRaise: the centred lift of limb 0 into the limbs above it folded into their column-forward
+// pass, as k_rescale_col folds the rescale's spread.  x0 [polys][N] holds INTT_0(limb 0), below
+// q_0; the tile of limb l (1 <= l < nl) loads x0's columns and lifts them in registers,
+//   v = ((x0 + h) mod q_0 - h) mod q_l,  h = q_0 / 2   (galois.hip k_modraise_spread, the path of
+// wide contexts)
+// before the column-forward stages, writing limb l of dst [polys][nl][N]; limb 0 is left to the
+// caller (a copy of the input's).  q_l may be far below q_0 (a 60-bit q_0 over 50-bit primes), so
+// both the lifted word and h go through reduce_word: h mod q_l is two Shoup products per workgroup.
+template <int LOGN, int H>
+__global__ __launch_bounds__(kColThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void
+k_modraise_col(const u64* __restrict__ x0, u64* __restrict__ dst, u32 nl, u32 items,
+               const ulonglong2* __restrict__ tw_all, const ModParams* __restrict__ mods) {
+  using G = Geo<LOGN>;
+  constexpr u64 N = 1ull << LOGN;
+  __shared__ u64 lds[G::LDS_CF];
+  const u32 sub = threadIdx.x % G::SUBS_C, t = threadIdx.x / G::SUBS_C;
+  const LViewC<G::SUBS_C> lv{lds + sub};
+  const u32 it = blockIdx.x;
+  if (it >= items) return;
+  // placement as k_rescale_col: with 8 | polys, XCD x takes the polys p = x mod 8 and runs the
+  // nl - 1 limbs of one (p, tile) back to back (x0's column tile from HBM once, then from the
+  // XCD's L2); otherwise limbs fastest over all XCDs
+  const u32 nq = nl - 1;
+  const u32 polys = items / (nq * G::TILES_C);
+  u32 tile, l, p;
+  if (polys % 8 == 0) {
+    const u32 k = it / 8;
+    l = k % nq;
+    tile = (k / nq) % G::TILES_C;
+    p = (k / (nq * G::TILES_C)) * 8 + it % 8;
+  } else {
+    l = it % nq;
+    tile = (it / nq) % G::TILES_C;
+    p = it / (nq * G::TILES_C);
+  }
+  l = __builtin_amdgcn_readfirstlane(l + 1);
+  const u64 col = (u64)tile * G::SUBS_C;
+  u64 x[kE];
+  pass_load<G::N1, true>(GView<G::R2>{const_cast<u64*>(x0) + (u64)p * N + col, sub}, t, x);
+  const ModParams m0 = mods[0], mi = mods[l];
+  const u64 h = m0.q >> 1, mh = mi.q - reduce_word(h, mi);
+#pragma unroll
+  for (int j = 0; j < kE; ++j) x[j] = csub(reduce_word(csub(x[j] + h, m0.q), mi) + mh, mi.q);
+  // scheduled from 2 (inputs are below q): the range launch_ntt_row_fwd_r2's row pass assumes
+  pass_run<G::N1, true, kNotFinal, kBlockSync, false, H, 2, false, false, G::HALF_C>(
+      x, GView<G::R2>{dst + ((u64)p * nl + l) * N + col, sub}, lv, t, tw_all + (u64)l * N, 1u, mi.q,
+      {0, 0}, {0, 0});
+}
+
+template <int LOGN, int HD>
+int modraise_col_dispatch(const fhe_ctx* c, const u64* x0, u64* dst, u32 polys, u32 nl,
+                          hipStream_t s) {
+  using G = Geo<LOGN>;
+  const u64 ic = (u64)polys * (nl - 1) * G::TILES_C;
+  if (int rc = check_grid(item_blocks(ic), G::THR_C, 1, 1, "modraise_col")) return rc;
+  k_modraise_col<LOGN, HD><<<item_grid(ic), G::THR_C, 0, s>>>(x0, dst, nl, (u32)ic, c->d_tw_fwd,
+                                                             c->d_mods);
+  return kOk;
+}
 #endif  // !FHE_NTT_KS_ONLY
 
 }  // namespace
@@ -2556,6 +2616,28 @@ int launch_rescale_col(const fhe_ctx* c, const u64* last, u64* dst, u32 polys, u
                          : rescale_col_dispatch<n, 8>(c, last, dst, polys, nq, half, s))  \
       return rc;                                              \
     FHE_HIP_CHECK(hipGetLastError());                         \
+    return kOk;
+    FHE_LOGN_CASES(X)
+#undef X
+  }
+  set_error("unsupported log_n");
+  return kUnsupported;
+}
+
+int launch_modraise_col(const fhe_ctx* c, const u64* x, u64* dst, u32 polys, u32 out_level,
+                        hipStream_t s) {
+  if (polys == 0 || out_level < 2) return kOk;
+  if (c->wide) {
+    set_error("modraise_col: the fused ModRaise needs every modulus < 2^61");
+    return kUnsupported;
+  }
+  switch (c->log_n) {
+#define X(n)                                                                        \
+  case n:                                                                           \
+    if (int rc = c->lz16 ? modraise_col_dispatch<n, 16>(c, x, dst, polys, out_level, s) \
+                         : modraise_col_dispatch<n, 8>(c, x, dst, polys, out_level, s))  \
+      return rc;                                                                    \
+    FHE_HIP_CHECK(hipGetLastError());                                               \
     return kOk;
     FHE_LOGN_CASES(X)
 #undef X

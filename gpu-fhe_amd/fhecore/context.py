@@ -771,6 +771,27 @@ class Context:
             self._one = self.encode_scalars([1], exact=True)
         return self.lincomb([ct], self._one, level=level, out=out)
 
+    # ---- ModRaise (fhe_mod_raise): from the bottom of the chain back up ---------------------
+    def mod_raise(self, ct, level=None, workspace=None, out=None):
+        """ct [..., 2, l, N] NTT form at any level l (only limb 0 is read) -> [..., 2, level, N]
+        (default: L): the centred lift of limb 0's coefficients reduced modulo every q_j, NTT form.
+        Limb 0 of the result is ct's; the result decrypts to m + q_0 I, I a small integer
+        polynomial (fhecore.polyeval.eval_mod removes it).  out must not overlap ct.  workspace:
+        fhe_mod_raise_workspace(ctx, batch) bytes; None takes the context's internal one, which is
+        refused while a Graph is capturing."""
+        lv = self._ct_level(ct, "mod_raise")
+        level = self.L if level is None else int(level)  # range-checked by fhe_mod_raise
+        batch = ct.numel() // (2 * lv * self.n)
+        shape = (*ct.shape[:-2], level, self.n)
+        if out is None:
+            out = _empty(shape, dtype=ct.dtype, device=ct.device)
+        else:
+            _check_out(out, ct, shape, "mod_raise: out")
+        with torch.cuda.device(self.device):
+            check(load().fhe_mod_raise(self._ptr, _ptr(out), _ptr(ct), lv, level, batch,
+                                       _ptr(workspace), _stream(ct)), "fhe_mod_raise")
+        return out
+
     # ---- SURVEY.md §8(f) row 2: wire format ----------------------------------------------
     def serialize(self, x, ntt_form: bool, limb0: int = 0) -> bytes:
         """x [..., nlimbs, N] over limbs [limb0, limb0 + nlimbs) -> an FHEC v1 blob."""

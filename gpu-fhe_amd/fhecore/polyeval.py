@@ -2,6 +2,8 @@
 composed on the host from mul_relin and lincomb (include/fhecore.h; no C entry of its own).
 
     chebyshev_eval(backend, ct, coeffs)  ->  sum_{j <= d} coeffs[j] T_j(x),  slots x in [-1, 1]
+    eval_mod(backend, ct, K, degree, double_angles)  ->  sin(2 pi K x) / (2 pi)   (EvalMod itself:
+        the series of a scaled cosine, then double-angle steps; at the end of this file)
 
 Baby steps T_1 .. T_m (m a power of two, m^2 >= d + 1) and giants T_2m, T_4m, ... come from
 T_2a = 2 T_a^2 - 1 and T_a+b = 2 T_a T_b - T_a-b, each one mul_relin(rescale) and one lincomb; T_k
@@ -203,3 +205,45 @@ def chebyshev_eval(backend, ct: Ct, coeffs, target_scale=None) -> Ct:
     ev.leaf_level = min(ev.T[j].level for j in range(1, m))
     scale = Fraction(ct.scale if target_scale is None else target_scale)
     return ev.run(c, g, scale)
+
+
+def eval_mod_levels(degree: int, double_angles: int) -> int:
+    """Levels eval_mod consumes: the Chebyshev series, then one per double-angle step."""
+    return levels_needed(degree) + double_angles
+
+
+def eval_mod(backend, ct: Ct, K: int, degree: int = 31, double_angles: int = 2) -> Ct:
+    """sin(2 pi K v) / (2 pi) on the slots v of ct (real, in [-1, 1]; chebyshev_eval's contract):
+    for K v = I + eps with I an integer -- a ciphertext after mod_raise and CoeffToSlot, scaled
+    into [-1, 1] -- this is eps up to (2 pi)^2 |eps|^3 / 6: the q_0 I term is gone.
+
+    With r = double_angles: the Chebyshev interpolant of cos((2 pi K v - pi / 2) / 2^r) of the
+    given degree (chebyshev_eval at its default target scale), then r double-angle steps
+    cos 2a = 2 cos^2 a - 1, each one mul_relin(rescale) and one lincomb -- the even branch of the
+    evaluator's T_2a -- which end at cos(2 pi K v - pi / 2) = sin(2 pi K v).  The factor 1 / (2 pi)
+    is a change of the declared scale (scale * 2 pi, the float 2 pi as an exact Fraction): no level
+    and no multiplication.  Consumes eval_mod_levels(degree, double_angles) levels; ValueError
+    before any work if the input has fewer to give, or K < 1."""
+    import math
+
+    import numpy as np
+
+    r = int(double_angles)
+    if K < 1 or r < 0:
+        raise ValueError("eval_mod: K must be at least 1 and double_angles non-negative")
+    if 0 <= degree <= 63:  # (another degree is chebyshev_eval's error)
+        need = eval_mod_levels(degree, r)
+        if ct.level - need < 1 or ct.level > len(backend.moduli):
+            raise ValueError(f"eval_mod: degree {degree} with {r} double angles consumes {need} "
+                             f"levels and the input is at level {ct.level}: too few levels")
+    w, div = 2.0 * math.pi * K, float(1 << r)
+    c = np.polynomial.chebyshev.chebinterpolate(lambda v: np.cos((w * v - math.pi / 2) / div),
+                                                degree)
+    out = chebyshev_eval(backend, ct, [Fraction(float(v)) for v in c])
+    q = [int(m) for m in backend.moduli]
+    for _ in range(r):  # cos 2a = 2 cos^2 a - 1
+        d = backend.mul_relin(out.data, out.data, True)
+        p = Ct(d, out.level - 1, out.scale * out.scale / q[out.level - 1])
+        d = backend.lincomb([p.data], [2, -round(p.scale)], True, False, p.level)
+        out = Ct(d, p.level, p.scale)
+    return Ct(out.data, out.level, out.scale * Fraction(2.0 * math.pi))

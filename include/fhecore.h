@@ -516,6 +516,24 @@ int fhe_mul_plain_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* ct, c
                         uint32_t pt_rows, uint32_t pt_batch, uint32_t level, uint32_t batch,
                         int rescale, void* workspace, fhe_stream_t stream);
 
+/* ---- ModRaise: from the bottom of the modulus chain back up (CKKS bootstrapping) ------------
+ * in is [batch][2][in_level][N], NTT form, canonical residues; only limb 0 of each polynomial is
+ * read, through its own stride (a ciphertext at any level is raised without a copy).  out is
+ * [batch][2][out_level][N], 1 <= out_level <= L, and for every polynomial p and limb l < out_level
+ *   x = INTT_0(in[p][0])                        coefficient form, 0 <= x < q_0
+ *   c = x if x <= (q_0 - 1) / 2, else x - q_0   the centred representative
+ *   out[p][l] = NTT_l(c mod q_l)                canonical residues
+ * so out[p][0] equals in[p][0] bit for bit, and the raised ciphertext decrypts to m + q_0 I for a
+ * small integer polynomial I (|I| <= (||s||_1 + 2) / 2), which EvalMod (fhecore.polyeval.eval_mod)
+ * removes.  q_l may be smaller or larger than q_0 and of another bit size.
+ * FHE_EINVAL before any launch: a null context or pointer; in_level or out_level of 0 or above L;
+ * any overlap of out with in; workspace == NULL while the stream is capturing.  batch == 0 is a
+ * no-op.  Workspace: fhe_mod_raise_workspace(ctx, batch) bytes (2 batch N words); NULL = internal.
+ * Capture-safe with an explicit workspace: nothing is allocated or synchronised. */
+size_t fhe_mod_raise_workspace(const fhe_ctx* ctx, uint32_t batch);
+int fhe_mod_raise(const fhe_ctx* ctx, uint64_t* out, const uint64_t* in, uint32_t in_level,
+                  uint32_t out_level, uint32_t batch, void* workspace, fhe_stream_t stream);
+
 /* ---- HIP graphs: capture a sequence of libfhecore calls on `stream` and replay it -----------
  * Between fhe_graph_begin and fhe_graph_end every call that takes a workspace must be given an
  * explicit one: with workspace == NULL a call returns FHE_EINVAL while the stream is capturing

@@ -478,6 +478,20 @@ class Evaluator {
     }
     return lincomb({&ct}, ones_, ctx_.L(), false, false, level);
   }
+  // ModRaise (fhe_mod_raise): ct at any level (only limb 0 is read) -> out_level limbs holding the
+  // centred lift of limb 0's coefficients modulo every q_j; limb 0 is ct's.
+  Ciphertext mod_raise(const Ciphertext& ct, uint32_t out_level) const {
+    if (ct.components != 2 || !ct.ntt_form)
+      throw Error(FHE_EINVAL, "mod_raise: need a 2-component NTT-form ciphertext");
+    if (out_level == 0 || out_level > ctx_.L())
+      throw Error(FHE_EINVAL, "mod_raise: out_level must be in [1, L]");
+    Ciphertext out(ctx_, 2, out_level, true);
+    const size_t need = fhe_mod_raise_workspace(ctx_.get(), 1);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    check(fhe_mod_raise(ctx_.get(), out.data(), ct.data(), ct.limbs, out_level, 1, ws_.data(), s_),
+          "fhe_mod_raise");
+    return out;
+  }
 
  private:
   uint64_t* plain_ws() const {
