@@ -3,6 +3,7 @@
 #include "../../include/fhecore.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <string>
 
@@ -741,6 +742,100 @@ int fhe_mod_raise(const fhe_ctx* c, uint64_t* out, const uint64_t* in, uint32_t 
   // same bits; tools/modraise_times.py times the two against each other)
   const char* u = std::getenv("FHECORE_MODRAISE_UNFUSED");
   return launch_mod_raise(c, out, in, in_level, out_level, batch, ws, u && u[0] == '1', hs(s));
+}
+
+size_t fhe_encode_workspace(const fhe_ctx* c, uint32_t count) {
+  return c ? encode_workspace_bytes(c, count) : 0;
+}
+
+int fhe_encode_roots(uint32_t log_n, double* out) {
+  if (log_n < 10 || log_n > 17) {
+    set_error("fhe_encode_roots: log_n must be in [10, 17]");
+    return kUnsupported;
+  }
+  if (!out) {
+    set_error("fhe_encode_roots: null output");
+    return kInvalid;
+  }
+  encode_roots(log_n, out);
+  return kOk;
+}
+
+int fhe_encode(const fhe_ctx* c, uint64_t* out, const double* slots, double delta, uint32_t level,
+               int special, uint32_t count, void* ws, fhe_stream_t s) {
+  // (the scale first: it needs no context, so a CPU-only machine can check the refusal)
+  if (!(std::isfinite(delta) && delta > 0)) {
+    set_error("fhe_encode: delta must be finite and positive");
+    return kInvalid;
+  }
+  if (!c) {
+    set_error("fhe_encode: null context");
+    return kInvalid;
+  }
+  if (level == 0 || level > c->L) {
+    set_error("fhe_encode: level must be in [1, L]");
+    return kInvalid;
+  }
+  if (special && c->K == 0) {
+    set_error("fhe_encode: special needs a context with P-limbs (K > 0)");
+    return kInvalid;
+  }
+  if (!out || !slots) {
+    set_error("fhe_encode: null data pointer");
+    return kInvalid;
+  }
+  const uint64_t rows = level + (special ? c->K : 0);
+  if (spans_overlap(out, (uint64_t)count * rows * c->n, reinterpret_cast<const uint64_t*>(slots),
+                    (uint64_t)count * c->n)) {
+    set_error("fhe_encode: out overlaps slots");
+    return kInvalid;
+  }
+  if (count == 0) return kOk;
+  int rc = ensure_ws(c, encode_workspace_bytes(c, count), &ws, hs(s));
+  if (rc) return rc;
+  // FHECORE_ENCODE_UNFUSED=1: the separate-spread form of wide contexts on any context (the same
+  // bits; tools/encode_times.py times the two against each other)
+  const char* u = std::getenv("FHECORE_ENCODE_UNFUSED");
+  return launch_encode(c, out, slots, delta, level, special != 0, count, ws, u && u[0] == '1',
+                       hs(s));
+}
+
+size_t fhe_decode_workspace(const fhe_ctx* c, uint32_t count) {
+  return c ? decode_workspace_bytes(c, count) : 0;
+}
+
+int fhe_decode(const fhe_ctx* c, double* slots, const uint64_t* pt, double delta, uint32_t pt_rows,
+               uint32_t level, uint32_t count, void* ws, fhe_stream_t s) {
+  // (the scale first: it needs no context, so a CPU-only machine can check the refusal)
+  if (!(std::isfinite(delta) && delta > 0)) {
+    set_error("fhe_decode: delta must be finite and positive");
+    return kInvalid;
+  }
+  if (!c) {
+    set_error("fhe_decode: null context");
+    return kInvalid;
+  }
+  if (level == 0 || level > c->L) {
+    set_error("fhe_decode: level must be in [1, L]");
+    return kInvalid;
+  }
+  if (pt_rows < std::min<uint32_t>(level, 2)) {
+    set_error("fhe_decode: pt_rows must cover the limbs read (min(level, 2))");
+    return kInvalid;
+  }
+  if (!slots || !pt) {
+    set_error("fhe_decode: null data pointer");
+    return kInvalid;
+  }
+  if (spans_overlap(reinterpret_cast<const uint64_t*>(slots), (uint64_t)count * c->n, pt,
+                    (uint64_t)count * pt_rows * c->n)) {
+    set_error("fhe_decode: slots overlaps pt");
+    return kInvalid;
+  }
+  if (count == 0) return kOk;
+  int rc = ensure_ws(c, decode_workspace_bytes(c, count), &ws, hs(s));
+  if (rc) return rc;
+  return launch_decode(c, slots, pt, delta, pt_rows, level, count, ws, hs(s));
 }
 
 }  // extern "C"

@@ -104,6 +104,16 @@ int ctx_create(fhe_ctx** out, u32 log_n, const u64* q, u32 L, const u64* p, u32 
     c->psi[i] = ntt_tables(mods[i], log_n, &twf[i * n], &twi[i * n], &nfold[4 * i],
                            split9 && i < L ? &twf9[i * n] : nullptr);
   }
+  // encode / decode (encode.hip): the special FFT's roots and rotation-group powers, and
+  // q_0^-1 mod q_1 for decode's two-limb centring
+  std::vector<double> roots(4 * n);
+  std::vector<u32> rot(n / 2);
+  encode_roots(log_n, roots.data());
+  encode_rot(log_n, rot.data());
+  if (L >= 2) {
+    const Pair64 inv = shoup_pair(powmod_u64(mods[0] % mods[1], mods[1] - 2, mods[1]), mods[1]);
+    c->enc_q0inv = make_ulonglong2(inv.x, inv.y);
+  }
   int rc = kOk;
   if ((rc = upload(&c->d_mods, c->mods_host.data(), M)) ||
       (rc = upload(&c->d_tw_fwd, reinterpret_cast<const ulonglong2*>(twf.data()), M * n)) ||
@@ -111,6 +121,8 @@ int ctx_create(fhe_ctx** out, u32 log_n, const u64* q, u32 L, const u64* p, u32 
       (rc = upload(&c->d_nfold, reinterpret_cast<const ulonglong2*>(nfold.data()), 4 * M)) ||
       (split9 && (rc = upload(&c->d_tw_fwd9, reinterpret_cast<const ulonglong2*>(twf9.data()),
                               (size_t)L * n))) ||
+      (rc = upload(&c->d_enc_roots, reinterpret_cast<const double2*>(roots.data()), 2 * n)) ||
+      (rc = upload(&c->d_enc_rot, rot.data(), n / 2)) ||
       (rc = build_rns_tables(c)) ||
       (rc = build_galois_tables(c))) {
     ctx_destroy(c);
@@ -131,7 +143,8 @@ int ctx_destroy(fhe_ctx* c) {
                     (void*)c->d_moddown_hat_wp, (void*)c->d_rpinv, (void*)c->d_pinv, (void*)c->d_rs_tab,
                     (void*)c->d_rs_half, (void*)c->d_lvl_inv, (void*)c->d_lvl_hat,
                     (void*)c->d_lvl_hat_w, (void*)c->d_lvl_hat_rw, (void*)c->d_lvl_hat_rwp,
-                    (void*)c->d_lvl_nfold_up, c->workspace})
+                    (void*)c->d_lvl_nfold_up, (void*)c->d_enc_roots, (void*)c->d_enc_rot,
+                    c->workspace})
     if (ptr) (void)hipFree(ptr);
   delete c;
   return kOk;

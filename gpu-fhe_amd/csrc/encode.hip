@@ -1,0 +1,319 @@
+// CKKS encode / decode on the device (fhe_encode / fhe_decode): the special FFT over the rotation
+// group in float64, the lift of the rounded coefficients into residues, and the two-limb centring
+// of a plaintext back into doubles.  tests/encode_ref.py restates every step; the results agree
+// with it bit for bit, which needs each butterfly to be exactly
+//   (dr wr - di wi, dr wi + di wr)   four rounded products, two rounded sums
+// so this translation unit is compiled with floating-point contraction off (no FMA).
+//
+// Organisation.  n = N / 2 complex points per plaintext, 16 bytes each.  One workgroup runs up to
+// kTileLog radix-2 stages on a tile of 2^kTileLog points in LDS (32 KiB).  n <= 2^kTileLog
+// (N <= 2^12): one pass.  Above: two passes over a workspace [count][n] that stays in cache
+//   strided     the top ln - kTileLog stages; a tile is 2^B rows of 2^C contiguous points
+//               (B + C = kTileLog), the rows 2^(ln - B) points apart
+//   contiguous  the low kTileLog stages on 2^kTileLog consecutive points
+// Encode (decimation in frequency, stages len = n .. 2) runs strided then contiguous and folds
+// the bit reversal, the scaling and the rounding into the contiguous pass's stores; decode
+// (decimation in time, len = 2 .. n) folds the bit reversal into the contiguous pass's loads and
+// the division by delta into the strided pass's stores.
+#pragma clang fp contract(off)
+
+#include <cmath>
+
+#include "internal.hpp"
+
+namespace fhe {
+namespace {
+
+constexpr int kTileLog = 11;
+constexpr int kFftThreads = 256;
+// LDS index of tile element e: one 16-byte pad per 16 elements, so that the power-of-two strides
+// of the low stages spread over the 256-byte bank row
+__device__ __forceinline__ u32 lpad(u32 e) { return e + (e >> 4); }
+constexpr u32 kTileLds = (1u << kTileLog) + (1u << (kTileLog - 4));
+
+enum InMode : int { kInComplex = 0, kInCoeff = 1 };
+enum OutMode : int { kOutComplex = 0, kOutRound = 1, kOutDivide = 2 };
+
+struct FftPass {
+  const void* in;   // kInComplex: double2 [count][n]; kInCoeff: double [count][N], gathered
+  void* out;        // kOutComplex / kOutDivide: double2 [count][n]; kOutRound: int64 [count][N]
+  const double2* roots;  // [2N]
+  const u32* rot;        // [n] 5^j mod 2N
+  double scale;          // kOutRound: delta / n; kOutDivide: delta
+  u32 ln;                // log2 n
+  u32 T;                 // log2 of the tile
+  u32 C;                 // log2 of the contiguous run of a tile row (T: the contiguous pass)
+  u32 b_lo;              // global bit of the pass's lowest stage (lh = 2^b_lo)
+  u32 B;                 // stages
+  u32 tiles;             // tiles per plaintext, n >> T
+  int in_mode, out_mode;
+};
+
+__device__ __forceinline__ u32 brev(u32 x, u32 bits) { return __brev(x) >> (32 - bits); }
+
+// ENC: the inverse special FFT of encode; otherwise the forward one of decode.
+template <bool ENC>
+__global__ __launch_bounds__(kFftThreads) void k_sfft_pass(const FftPass a) {
+  __shared__ double2 lds[kTileLds];
+  const u32 tl = blockIdx.x % a.tiles, p = blockIdx.x / a.tiles;
+  const u32 n = 1u << a.ln, T = a.T, C = a.C;
+  const bool strided = C < T;
+  // strided: tile = (hi, chunk of 2^C within the 2^b_lo low indices); rows 2^b_lo apart
+  const u32 lc_bits = strided ? a.b_lo - C : 0;
+  const u32 base = strided ? ((tl >> lc_bits) << (a.b_lo + a.B)) + ((tl & ((1u << lc_bits) - 1)) << C)
+                           : tl << T;
+  const u32 cmask = (1u << C) - 1;
+  const u32 lb = strided ? C : 0;  // local bit of the pass's lowest stage
+  auto gidx = [&](u32 e) { return strided ? base + ((e >> C) << a.b_lo) + (e & cmask) : base + e; };
+
+  for (u32 e = threadIdx.x; e < (1u << T); e += kFftThreads) {
+    const u32 g = gidx(e);
+    double2 v;
+    if (a.in_mode == kInCoeff) {
+      const double* x = static_cast<const double*>(a.in) + (u64)p * 2 * n;
+      const u32 k = brev(g, a.ln);
+      v = make_double2(x[k], x[k + n]);
+    } else {
+      v = static_cast<const double2*>(a.in)[(u64)p * n + g];
+    }
+    lds[lpad(e)] = v;
+  }
+  __syncthreads();
+
+  for (u32 st = 0; st < a.B; ++st) {
+    const u32 i = ENC ? a.B - 1 - st : st;
+    const u32 pb = lb + i;       // local bit of this stage's half length
+    const u32 gb = a.b_lo + i;   // lh = 2^gb, lq = 8 lh
+    const u32 lqm = (8u << gb) - 1, wsh = a.ln - 1 - gb;
+    for (u32 k = threadIdx.x; k < (1u << (T - 1)); k += kFftThreads) {
+      const u32 ea = ((k >> pb) << (pb + 1)) | (k & ((1u << pb) - 1));
+      const u32 eb = ea + (1u << pb);
+      const u32 j = gidx(ea) & ((1u << gb) - 1);
+      const u32 r = a.rot[j] & lqm;
+      const double2 w = a.roots[(ENC ? lqm + 1 - r : r) << wsh];
+      const double2 x = lds[lpad(ea)], y = lds[lpad(eb)];
+      double2 s, d;
+      if (ENC) {
+        s = make_double2(x.x + y.x, x.y + y.y);
+        const double dr = x.x - y.x, di = x.y - y.y;
+        const double p1 = dr * w.x, p2 = di * w.y, p3 = dr * w.y, p4 = di * w.x;
+        d = make_double2(p1 - p2, p3 + p4);
+      } else {
+        const double p1 = y.x * w.x, p2 = y.y * w.y, p3 = y.x * w.y, p4 = y.y * w.x;
+        const double br = p1 - p2, bi = p3 + p4;
+        s = make_double2(x.x + br, x.y + bi);
+        d = make_double2(x.x - br, x.y - bi);
+      }
+      lds[lpad(ea)] = s;
+      lds[lpad(eb)] = d;
+    }
+    __syncthreads();
+  }
+
+  for (u32 e = threadIdx.x; e < (1u << T); e += kFftThreads) {
+    const u32 g = gidx(e);
+    const double2 v = lds[lpad(e)];
+    if (a.out_mode == kOutRound) {
+      long long* c = static_cast<long long*>(a.out) + (u64)p * 2 * n;
+      const u32 k = brev(g, a.ln);
+      c[k] = (long long)rint(v.x * a.scale);
+      c[k + n] = (long long)rint(v.y * a.scale);
+    } else if (a.out_mode == kOutDivide) {
+      static_cast<double2*>(a.out)[(u64)p * n + g] = make_double2(v.x / a.scale, v.y / a.scale);
+    } else {
+      static_cast<double2*>(a.out)[(u64)p * n + g] = v;
+    }
+  }
+}
+
+template <bool ENC>
+int launch_pass(const FftPass& a, u32 count, hipStream_t s) {
+  const u64 blocks = (u64)a.tiles * count;
+  if (int rc = check_grid(blocks, kFftThreads, 1, 1, ENC ? "encode" : "decode")) return rc;
+  k_sfft_pass<ENC><<<dim3((u32)blocks), kFftThreads, 0, s>>>(a);
+  FHE_HIP_CHECK(hipGetLastError());
+  return kOk;
+}
+
+// The special FFT of `count` plaintexts: ENC slots -> int64 coefficients [count][N] (scale =
+// delta / n), else doubles [count][N] -> slots (scale = delta).  work [count][n] complex, used by
+// the two-pass sizes only.
+template <bool ENC>
+int launch_sfft(const fhe_ctx* c, const void* in, void* out, double2* work, double scale,
+                u32 count, hipStream_t s) {
+  const u32 ln = c->log_n - 1;
+  FftPass a{};
+  a.roots = c->d_enc_roots;
+  a.rot = c->d_enc_rot;
+  a.scale = scale;
+  a.ln = ln;
+  a.T = std::min<u32>(ln, kTileLog);
+  a.tiles = 1u << (ln - a.T);
+  const FftPass contiguous = [&] {
+    FftPass x = a;
+    x.C = x.T;
+    x.b_lo = 0;
+    x.B = x.T;
+    return x;
+  }();
+  if (ln <= (u32)kTileLog) {
+    FftPass x = contiguous;
+    x.in = in;
+    x.out = out;
+    x.in_mode = ENC ? kInComplex : kInCoeff;
+    x.out_mode = ENC ? kOutRound : kOutDivide;
+    return launch_pass<ENC>(x, count, s);
+  }
+  FftPass strided = a;
+  strided.B = ln - kTileLog;
+  strided.C = kTileLog - strided.B;
+  strided.b_lo = kTileLog;
+  FftPass first = ENC ? strided : contiguous, second = ENC ? contiguous : strided;
+  first.in = in;
+  first.out = work;
+  first.in_mode = ENC ? kInComplex : kInCoeff;
+  first.out_mode = kOutComplex;
+  second.in = work;
+  second.out = out;
+  second.in_mode = kInComplex;
+  second.out_mode = ENC ? kOutRound : kOutDivide;
+  if (int rc = launch_pass<ENC>(first, count, s)) return rc;
+  return launch_pass<ENC>(second, count, s);
+}
+
+// row r of an encoded plaintext -> context limb: the Q-limbs 0 .. level-1, then the P-limbs
+__device__ __forceinline__ u32 enc_limb(u32 r, u32 level, u32 L) {
+  return r < level ? r : L + (r - level);
+}
+
+// The unfused lift (wide contexts): coefficients [count][N] -> out [count][rows][N], canonical
+// residues of every row's limb, to be NTT'd in place.  Grid y = row, z = plaintext.
+__global__ __launch_bounds__(kFftThreads) void k_encode_spread(u64* __restrict__ out,
+                                                               const long long* __restrict__ cf,
+                                                               u32 rows, u32 level, u32 L,
+                                                               u32 log_n,
+                                                               const ModParams* __restrict__ mods) {
+  const u64 n = 1ull << log_n;
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 r = blockIdx.y;
+  const u64 p = blockIdx.z;
+  const ModParams m = mods[enc_limb(r, level, L)];
+  const long long v = cf[p * n + i];
+  const u64 mag = v < 0 ? 0 - (u64)v : (u64)v;
+  const u64 res = reduce_word(mag, m);
+  out[(p * rows + r) * n + i] = (v < 0 && res != 0) ? m.q - res : res;
+}
+
+// Decode's centring: x [count][nl][N] = INTT of limb 0 (and limb 1 when nl == 2) -> the centred
+// value over q_0 (q_0 q_1) as one round-to-nearest-even double, d [count][N].
+__global__ __launch_bounds__(kFftThreads) void k_decode_centre(double* __restrict__ d,
+                                                               const u64* __restrict__ x, u32 nl,
+                                                               u32 log_n, ulonglong2 q0inv,
+                                                               const ModParams* __restrict__ mods) {
+  const u64 n = 1ull << log_n;
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u64 p = blockIdx.y;
+  const u64 q0 = mods[0].q;
+  const u64 x0 = x[(p * nl) * n + i];
+  u128 mag;
+  bool neg;
+  if (nl == 1) {
+    neg = x0 > (q0 - 1) / 2;
+    mag = neg ? q0 - x0 : x0;
+  } else {
+    const ModParams m1 = mods[1];
+    const u64 x1 = x[(p * nl + 1) * n + i];
+    const u64 a0 = reduce_word(x0, m1);
+    const u64 df = x1 >= a0 ? x1 - a0 : x1 + m1.q - a0;
+    const u64 t = csub(shoup_lazy(df, q0inv.x, q0inv.y, m1.q), m1.q);
+    const u128 Q = (u128)q0 * m1.q;
+    const u128 V = (u128)x0 + (u128)q0 * t;
+    neg = V > (Q - 1) / 2;
+    mag = neg ? Q - V : V;
+  }
+  // |V| -> double with one rounding: the top 64 bits in one word, the dropped bits' sticky OR'd
+  // into bit 0 (the word's own conversion then rounds to nearest even as the 128-bit value would)
+  const u64 hi = (u64)(mag >> 64);
+  double v;
+  if (hi == 0) {
+    v = (double)(u64)mag;
+  } else {
+    const int sh = 64 - __clzll((long long)hi);
+    u64 w = (u64)(mag >> sh);
+    if ((u64)mag << (64 - sh)) w |= 1;
+    v = ldexp((double)w, sh);
+  }
+  d[p * n + i] = neg ? -v : v;
+}
+
+}  // namespace
+
+size_t encode_workspace_bytes(const fhe_ctx* c, u32 count) {
+  // the FFT's workspace [count][n] complex, then the coefficients [count][N]
+  return (size_t)2 * count * c->n * sizeof(u64);
+}
+
+size_t decode_workspace_bytes(const fhe_ctx* c, u32 count) {
+  // INTT of limbs 0, 1 [count][2][N] (the FFT's workspace afterwards), then the doubles [count][N]
+  return (size_t)3 * count * c->n * sizeof(u64);
+}
+
+int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta, u32 level,
+                  bool special, u32 count, void* ws, bool unfused, hipStream_t s) {
+  if (count == 0) return kOk;
+  const u64 n = c->n;
+  const u32 rows = level + (special ? c->K : 0);
+  double2* work = static_cast<double2*>(ws);
+  long long* cf = reinterpret_cast<long long*>(static_cast<u64*>(ws) + (u64)count * n);
+  const double scale = delta / (double)(n / 2);
+  int rc;
+  if ((rc = launch_sfft<true>(c, slots, cf, work, scale, count, s))) return rc;
+  prof_mark(s, "encode_fft");
+  const u64 ps = (u64)rows * n;
+  if (!c->wide && !unfused) {
+    // the lift rides on the column-forward pass (ntt.hip k_encode_col); the row pass runs in place
+    if ((rc = launch_encode_col(c, reinterpret_cast<const u64*>(cf), out, count, level, rows, s)))
+      return rc;
+    if ((rc = launch_ntt_row_fwd_r2(c, out, ps, out, ps, count, 0, level, s))) return rc;
+    if (special &&
+        (rc = launch_ntt_row_fwd_r2(c, out + (u64)level * n, ps, out + (u64)level * n, ps, count,
+                                    c->L, c->K, s)))
+      return rc;
+  } else {
+    if ((rc = check_grid(n / kFftThreads, kFftThreads, rows, count, "encode"))) return rc;
+    k_encode_spread<<<dim3((u32)(n / kFftThreads), rows, count), kFftThreads, 0, s>>>(
+        out, cf, rows, level, c->L, c->log_n, c->d_mods);
+    FHE_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_ntt(c, true, out, out, count, ps, 0, level, s))) return rc;
+    if (special && (rc = launch_ntt(c, true, out + (u64)level * n, out + (u64)level * n, count, ps,
+                                    c->L, c->K, s)))
+      return rc;
+  }
+  prof_mark(s, "encode_ntt");
+  return kOk;
+}
+
+int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 pt_rows,
+                  u32 level, u32 count, void* ws, hipStream_t s) {
+  if (count == 0) return kOk;
+  const u64 n = c->n;
+  const u32 nl = level >= 2 ? 2 : 1;
+  u64* x = static_cast<u64*>(ws);  // [count][nl][N]
+  double* d = reinterpret_cast<double*>(x + (u64)2 * count * n);
+  int rc;
+  if ((rc = launch_ntt_strided(c, false, pt, (u64)pt_rows * n, x, (u64)nl * n, count, 0, nl, s)))
+    return rc;
+  prof_mark(s, "decode_intt");
+  if ((rc = check_grid(n / kFftThreads, kFftThreads, count, 1, "decode"))) return rc;
+  k_decode_centre<<<dim3((u32)(n / kFftThreads), count), kFftThreads, 0, s>>>(
+      d, x, nl, c->log_n, c->enc_q0inv, c->d_mods);
+  FHE_HIP_CHECK(hipGetLastError());
+  prof_mark(s, "decode_centre");
+  // x is dead: its region is the FFT's workspace
+  if ((rc = launch_sfft<false>(c, d, slots, reinterpret_cast<double2*>(x), delta, count, s)))
+    return rc;
+  prof_mark(s, "decode_fft");
+  return kOk;
+}
+
+}  // namespace fhe

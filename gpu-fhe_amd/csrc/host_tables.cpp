@@ -2,6 +2,7 @@
 #include "host_tables.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <numeric>
 
 namespace fhe {
@@ -222,6 +223,24 @@ void conv_tables(const std::vector<u64>& mods, u32 s0, u32 S, std::vector<Pair64
       // the Montgomery form for its Montgomery-reduced sums (S < 8)
       hat[(size_t)k * M + t] = Pair64{hm, (u64)(((u128)hm << 64) % tm)};
     }
+  }
+}
+
+void encode_roots(u32 log_n, double* out) {
+  const u64 n = 1ull << log_n;
+  for (u64 k = 0; k < 2 * n; ++k) {
+    const double a = M_PI * (double)k / (double)n;
+    out[2 * k] = std::cos(a);
+    out[2 * k + 1] = std::sin(a);
+  }
+}
+
+void encode_rot(u32 log_n, u32* out) {
+  const u64 m = 2ull << log_n;
+  u64 r = 1;
+  for (u64 j = 0; j < m / 4; ++j) {
+    out[j] = (u32)r;
+    r = r * 5 % m;
   }
 }
 

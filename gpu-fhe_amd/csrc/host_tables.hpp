@@ -40,4 +40,11 @@ void lane_major_rows(Pair64* tw, size_t entries, u32 log_n, int elog, int n1 = -
 void conv_tables(const std::vector<u64>& mods, u32 s0, u32 S, std::vector<Pair64>& inv,
                  std::vector<Pair64>& hat);
 
+// CKKS encode / decode (encode.hip): the special FFT's root table, out [2N][2] = (cos, sin) of
+// a_k = M_PI * (double)k / (double)N, every entry straight from libm (no symmetries: the Python
+// reference calls the same libm through math.cos / math.sin and gets the same bits), and the
+// rotation group's powers rot [N / 2] = 5^j mod 2N.
+void encode_roots(u32 log_n, double* out);
+void encode_rot(u32 log_n, u32* out);
+
 }  // namespace fhe

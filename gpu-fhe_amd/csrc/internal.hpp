@@ -119,6 +119,12 @@ struct fhe_ctx {
   // d_nfold_up per level: the entries of the last digit's limbs take that digit's (D^_k)^-1
   ulonglong2* d_lvl_nfold_up = nullptr;  // [L][L + K][4]
 
+  // encode / decode (encode.hip): (cos, sin)(pi k / N), k < 2N; 5^j mod 2N, j < N / 2; the Shoup
+  // pair of q_0^-1 mod q_1 (L >= 2)
+  double2* d_enc_roots = nullptr;
+  uint32_t* d_enc_rot = nullptr;
+  ulonglong2 enc_q0inv = {0, 0};
+
   void* workspace = nullptr;
   size_t workspace_bytes = 0;
   // the stream that last took the internal workspace (a call on another stream waits for the
@@ -286,6 +292,11 @@ int launch_rescale_col(const fhe_ctx* c, const u64* last, u64* dst, u32 polys, u
 // from 2: launch_ntt_row_fwd_r2 finishes them); limb 0 of dst is not touched.
 int launch_modraise_col(const fhe_ctx* c, const u64* x, u64* dst, u32 polys, u32 out_level,
                         hipStream_t s);
+// Encode, lift + column-forward pass in one (ntt.hip, k_encode_col): cf [polys][N] signed 64-bit
+// coefficients (|c| < 2^62) -> every row of dst [polys][rows][N] column-passed (schedule from 2:
+// launch_ntt_row_fwd_r2 finishes them); row r is limb r < level ? r : L + r - level.
+int launch_encode_col(const fhe_ctx* c, const u64* cf, u64* dst, u32 polys, u32 level, u32 rows,
+                      hipStream_t s);
 // Fused ct x ct tensor: a, b [batch][2][nlimbs][N] coefficient form -> d [batch][3][nlimbs][N].
 int launch_hommult(const fhe_ctx* c, u64* d, const u64* a, const u64* b, u32 batch, u32 limb0,
                    u32 nlimbs, void* ws, hipStream_t s);
@@ -472,6 +483,18 @@ int launch_linear_transform(const fhe_ctx* c, u64* out, const u64* in, u32 n1, u
                             const u64* const* giant_a, const u64* const* pt, u32 level,
                             u32 batch, void* ws, hipStream_t s);
 size_t linear_transform_workspace_bytes(const fhe_ctx* c, u32 n2, u32 batch);
+
+// ---- launchers (encode.hip): CKKS encode / decode ---------------------------------------
+// slots [count][N/2][2] doubles (re, im) -> out [count][level (+ K)][N] NTT form: the inverse
+// special FFT, c = rint(v delta / (N/2)), row r = NTT(c mod q_limb(r)).  unfused: a spread kernel
+// and whole NTTs (the form of wide contexts) on any context (tools/encode_times.py measures it).
+int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta, u32 level,
+                  bool special, u32 count, void* ws, bool unfused, hipStream_t s);
+size_t encode_workspace_bytes(const fhe_ctx* c, u32 count);
+// pt [count][pt_rows][N] NTT form (limbs 0 and, at level >= 2, 1 read) -> slots [count][N/2][2]
+int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 pt_rows,
+                  u32 level, u32 count, void* ws, hipStream_t s);
+size_t decode_workspace_bytes(const fhe_ctx* c, u32 count);
 
 // ---- launchers (pipeline.hip): SURVEY.md §8(f) row 4 -----------------------------------
 // (level: the Q-limbs of a / b, 1 .. L; the key stays the top-level one)

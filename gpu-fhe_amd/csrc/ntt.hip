@@ -2208,6 +2208,69 @@ int modraise_col_dispatch(const fhe_ctx* c, const u64* x0, u64* dst, u32 polys, 
                                                              c->d_mods);
   return kOk;
 }
+
+// Encode: the lift of the rounded coefficients into every row's residues folded into that row's
+// column-forward pass, as k_modraise_col folds ModRaise's.  cf [polys][N] holds signed 64-bit
+// coefficients c (|c| < 2^62 by the call's precondition; any word gives a canonical residue);
+// the tile of row r loads cf's columns and lifts them in registers,
+//   v = c mod q_limb(r)   (|c| through reduce_word, negated for c < 0, q itself folded to 0;
+//                          encode.hip k_encode_spread is the path of wide contexts)
+// before the column-forward stages, writing row r of dst [polys][rows][N].  Row r is limb
+// r < level ? r : L + r - level: the Q-limbs 0 .. level-1, then the P-limbs.
+template <int LOGN, int H>
+__global__ __launch_bounds__(kColThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void
+k_encode_col(const u64* __restrict__ cf, u64* __restrict__ dst, u32 rows, u32 level, u32 L,
+             u32 items, const ulonglong2* __restrict__ tw_all, const ModParams* __restrict__ mods) {
+  using G = Geo<LOGN>;
+  constexpr u64 N = 1ull << LOGN;
+  __shared__ u64 lds[G::LDS_CF];
+  const u32 sub = threadIdx.x % G::SUBS_C, t = threadIdx.x / G::SUBS_C;
+  const LViewC<G::SUBS_C> lv{lds + sub};
+  const u32 it = blockIdx.x;
+  if (it >= items) return;
+  // placement as k_rescale_col: with 8 | polys, XCD x takes the polys p = x mod 8 and runs the
+  // rows of one (p, tile) back to back (cf's column tile from HBM once, then from the XCD's L2);
+  // otherwise rows fastest over all XCDs
+  const u32 polys = items / (rows * G::TILES_C);
+  u32 tile, r, p;
+  if (polys % 8 == 0) {
+    const u32 k = it / 8;
+    r = k % rows;
+    tile = (k / rows) % G::TILES_C;
+    p = (k / (rows * G::TILES_C)) * 8 + it % 8;
+  } else {
+    r = it % rows;
+    tile = (it / rows) % G::TILES_C;
+    p = it / (rows * G::TILES_C);
+  }
+  r = __builtin_amdgcn_readfirstlane(r);
+  const u32 l = r < level ? r : L + (r - level);
+  const u64 col = (u64)tile * G::SUBS_C;
+  u64 x[kE];
+  pass_load<G::N1, true>(GView<G::R2>{const_cast<u64*>(cf) + (u64)p * N + col, sub}, t, x);
+  const ModParams mi = mods[l];
+#pragma unroll
+  for (int j = 0; j < kE; ++j) {
+    const bool neg = (int64_t)x[j] < 0;
+    const u64 res = reduce_word(neg ? 0 - x[j] : x[j], mi);
+    x[j] = (neg && res != 0) ? mi.q - res : res;
+  }
+  // scheduled from 2 (inputs are below q): the range launch_ntt_row_fwd_r2's row pass assumes
+  pass_run<G::N1, true, kNotFinal, kBlockSync, false, H, 2, false, false, G::HALF_C>(
+      x, GView<G::R2>{dst + ((u64)p * rows + r) * N + col, sub}, lv, t, tw_all + (u64)l * N, 1u,
+      mi.q, {0, 0}, {0, 0});
+}
+
+template <int LOGN, int HD>
+int encode_col_dispatch(const fhe_ctx* c, const u64* cf, u64* dst, u32 polys, u32 level, u32 rows,
+                        hipStream_t s) {
+  using G = Geo<LOGN>;
+  const u64 ic = (u64)polys * rows * G::TILES_C;
+  if (int rc = check_grid(item_blocks(ic), G::THR_C, 1, 1, "encode_col")) return rc;
+  k_encode_col<LOGN, HD><<<item_grid(ic), G::THR_C, 0, s>>>(cf, dst, rows, level, c->L, (u32)ic,
+                                                           c->d_tw_fwd, c->d_mods);
+  return kOk;
+}
 #endif  // !FHE_NTT_KS_ONLY
 
 }  // namespace
@@ -2638,6 +2701,28 @@ int launch_modraise_col(const fhe_ctx* c, const u64* x, u64* dst, u32 polys, u32
                          : modraise_col_dispatch<n, 8>(c, x, dst, polys, out_level, s))  \
       return rc;                                                                    \
     FHE_HIP_CHECK(hipGetLastError());                                               \
+    return kOk;
+    FHE_LOGN_CASES(X)
+#undef X
+  }
+  set_error("unsupported log_n");
+  return kUnsupported;
+}
+
+int launch_encode_col(const fhe_ctx* c, const u64* cf, u64* dst, u32 polys, u32 level, u32 rows,
+                      hipStream_t s) {
+  if (polys == 0 || rows == 0) return kOk;
+  if (c->wide) {
+    set_error("encode_col: the fused encode needs every modulus < 2^61");
+    return kUnsupported;
+  }
+  switch (c->log_n) {
+#define X(n)                                                                             \
+  case n:                                                                                \
+    if (int rc = c->lz16 ? encode_col_dispatch<n, 16>(c, cf, dst, polys, level, rows, s) \
+                         : encode_col_dispatch<n, 8>(c, cf, dst, polys, level, rows, s))  \
+      return rc;                                                                         \
+    FHE_HIP_CHECK(hipGetLastError());                                                    \
     return kOk;
     FHE_LOGN_CASES(X)
 #undef X

@@ -8,6 +8,11 @@ the slots by r (fhecore Context.galois_elt / rotate):
 
     encode:  m_k = round(delta * (2/N) Re(sum_j z_j zeta_j^-k))        (k < N)
     decode:  z_j = sum_k m_k zeta_j^k / delta,  m = CRT-centred residues
+
+This class stays the mathematical definition.  The device path -- Context.encode / decode /
+encode_diagonals (fhe_encode / fhe_decode) -- computes the same embedding with the special FFT over
+the rotation group and produces NTT-form plaintexts where the kernels read them; its coefficients
+differ from encode()'s by at most a unit of rounding (tests/test_encode_cpu.py).
 """
 from __future__ import annotations
 

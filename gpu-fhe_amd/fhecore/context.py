@@ -45,6 +45,15 @@ def default_params(log_n: int, L: int, K: int = 0):
     return m[:L], m[L:]
 
 
+def encode_roots(log_n: int) -> np.ndarray:
+    """The special FFT's root table of a context at ring degree 2^log_n (fhe_encode_roots; no
+    device needed): float64 [2N, 2], row k = (cos, sin)(pi k / N), the values the context uploads
+    for fhe_encode / fhe_decode."""
+    out = np.empty((2 << log_n, 2), dtype=np.float64)
+    check(load().fhe_encode_roots(log_n, out.ctypes.data_as(ctypes.c_void_p)), "fhe_encode_roots")
+    return out
+
+
 # ----------------------------------------------------------------------------- device helpers
 
 def _nonce(seed):
@@ -791,6 +800,96 @@ class Context:
             check(load().fhe_mod_raise(self._ptr, _ptr(out), _ptr(ct), lv, level, batch,
                                        _ptr(workspace), _stream(ct)), "fhe_mod_raise")
         return out
+
+    # ---- CKKS encode / decode on the device (fhe_encode / fhe_decode) -----------------------
+    def _slots(self, z, who):
+        if not isinstance(z, torch.Tensor):
+            z = torch.from_numpy(np.ascontiguousarray(np.asarray(z, dtype=np.complex128)))
+        if z.dtype != torch.complex128:
+            raise TypeError(f"{who}: expected complex128 slots, got {z.dtype}")
+        if z.shape[-1] != self.n // 2:
+            raise ValueError(f"{who}: expected [..., {self.n // 2}] slots, got {tuple(z.shape)}")
+        return z.to(self._dev()).contiguous()
+
+    def encode(self, z, delta, level=None, special=False, workspace=None, out=None):
+        """z complex128 [..., N/2] (a host array is moved to the device first) -> the plaintexts
+        [..., level (+ K), N] in NTT form (fhe_encode): the inverse special FFT over the rotation
+        group, c = rint(v delta / (N/2)), every row the NTT of c modulo its limb -- the Q-limbs
+        0 .. level-1 (default L) and, with special, the P-limbs after them.  level = L with special
+        is the [L + K, N] diagonal linear_transform / rotate_sum_hoisted read at every level;
+        special=False is the [level, N] plaintext of mul_plain / encrypt.  Slot j sits at the root
+        exp(i pi 5^j / N) as in fhecore.ckks.Encoder, whose coefficients this differs from by at
+        most a unit.  Precondition: |c| < 2^62.  workspace: fhe_encode_workspace(ctx, count) bytes;
+        None takes the context's internal one, which is refused while a Graph is capturing."""
+        z = self._slots(z, "encode")
+        level = self.L if level is None else int(level)  # range-checked by fhe_encode
+        rows = level + (self.K if special else 0)
+        count = z.numel() // (self.n // 2)
+        shape = (*z.shape[:-1], rows, self.n)
+        if out is None:
+            out = _empty(shape, dtype=torch.int64, device=z.device)
+        else:
+            _check_out(out, z, shape, "encode: out")
+        with torch.cuda.device(self.device):
+            check(load().fhe_encode(self._ptr, _ptr(out), _ptr(z), float(delta), level,
+                                    int(bool(special)), count, _ptr(workspace), _stream(z)),
+                  "fhe_encode")
+        return out
+
+    def decode(self, pt, delta, level=None, workspace=None, out=None):
+        """pt [..., rows, N] NTT form -> complex128 slots [..., N/2] (fhe_decode).  level (default:
+        min(rows, L)) says how many Q-limbs pt carries a value over; limb 0 is read, and limb 1 at
+        level >= 2, through the rows' own stride (an [L + K, N] diagonal decodes in place).  The
+        value is centred over q_0 q_1 (q_0 at level 1), so the plaintext's true centred value must
+        be below q_0 q_1 / 2 (q_0 / 2) in magnitude."""
+        _check_tensor(pt, "decode: pt")
+        if pt.dim() < 2 or pt.shape[-1] != self.n:
+            raise ValueError(f"decode: expected [..., rows, {self.n}], got {tuple(pt.shape)}")
+        rows = pt.shape[-2]
+        level = min(rows, self.L) if level is None else int(level)  # range-checked by fhe_decode
+        count = pt.numel() // (rows * self.n)
+        shape = (*pt.shape[:-2], self.n // 2)
+        if out is None:
+            out = _empty(shape, dtype=torch.complex128, device=pt.device)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.complex128 or \
+                    out.device != pt.device or not out.is_contiguous() or \
+                    tuple(out.shape) != shape:
+                raise ValueError(f"decode: out must be a contiguous complex128 {shape} tensor on "
+                                 "pt's device")
+        with torch.cuda.device(self.device):
+            check(load().fhe_decode(self._ptr, _ptr(out), _ptr(pt), float(delta), rows, level,
+                                    count, _ptr(workspace), _stream(pt)), "fhe_decode")
+        return out
+
+    def encode_diagonals(self, diags, n1: int, n2: int, delta, level=None):
+        """The plaintexts of a baby-step / giant-step matrix product from a slot matrix's
+        diagonals: diags maps k < n1 n2 to the complex [N/2] vector d_k[j] = A[j][(j + k) mod N/2]
+        (absent diagonals are zero).  Returns (baby_elts, giant_elts, pts) for linear_transform,
+        which then computes A z = sum_k d_k * rot_k(z).
+
+        Direction: rotate by galois_elt(step) moves slot j + step into slot j,
+        rot_step(z)[j] = z[(j + step) mod N/2] (numpy: np.roll(z, -step)).  With k = g n1 + b,
+        A z = sum_g rot_{g n1}(sum_b rot_{-g n1}(d_k) * rot_b(z)), so pts[g][b] encodes d_k rolled
+        towards higher indices by g n1 (torch.roll(d_k, g n1)), over Q u P at scale delta.  All
+        n1 n2 encodings are one fhe_encode call.  level is accepted for symmetry with the other
+        calls: the plaintexts are the top-level [L + K, N] ones, read in place at every level."""
+        if n1 < 1 or n2 < 1:
+            raise ValueError("encode_diagonals: n1, n2 >= 1")
+        if level is not None and not 1 <= int(level) <= self.L:
+            raise ValueError("encode_diagonals: level must be in [1, L]")
+        ns = self.n // 2
+        bad = [k for k in diags if not 0 <= int(k) < n1 * n2]
+        if bad:
+            raise ValueError(f"encode_diagonals: diagonal indices {bad} outside [0, n1 n2)")
+        z = torch.zeros(n2, n1, ns, dtype=torch.complex128, device=self._dev())
+        for k, d in diags.items():
+            g, b = divmod(int(k), n1)
+            z[g, b] = torch.roll(self._slots(d, "encode_diagonals").reshape(ns), g * n1)
+        enc = self.encode(z, delta, level=self.L, special=True)
+        baby = [self.galois_elt(b) for b in range(n1)]
+        giant = [self.galois_elt(g * n1) for g in range(n2)]
+        return baby, giant, [[enc[g, b] for b in range(n1)] for g in range(n2)]
 
     # ---- SURVEY.md §8(f) row 2: wire format ----------------------------------------------
     def serialize(self, x, ntt_form: bool, limb0: int = 0) -> bytes:

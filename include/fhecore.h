@@ -17,7 +17,9 @@
  *  - Return 0 on success, a negative FHE_E* code on error; fhe_last_error() (thread-local)
  *    describes the last failure.  No entry point aborts or throws.
  *  - Every data pointer is DEVICE memory owned by the caller.  Residues are uint64 in
- *    layout [poly][limb][N] (limb-major, each limb's N coefficients contiguous).
+ *    layout [poly][limb][N] (limb-major, each limb's N coefficients contiguous).  The only
+ *    other element type is the double: the complex slots of fhe_encode / fhe_decode,
+ *    [count][N/2][2] interleaved (re, im), and the host table of fhe_encode_roots.
  *  - `stream` is a hipStream_t (NULL = the legacy default stream).  Launches are
  *    asynchronous and capture-safe (no allocation or synchronisation inside) unless noted.
  *  - A context is immutable after creation: calls on different streams may share it.  Passing
@@ -533,6 +535,49 @@ int fhe_mul_plain_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* ct, c
 size_t fhe_mod_raise_workspace(const fhe_ctx* ctx, uint32_t batch);
 int fhe_mod_raise(const fhe_ctx* ctx, uint64_t* out, const uint64_t* in, uint32_t in_level,
                   uint32_t out_level, uint32_t batch, void* workspace, fhe_stream_t stream);
+
+/* ---- CKKS encode / decode on the device ------------------------------------------------------
+ * The canonical embedding over the rotation group (slot j at the root exp(i pi 5^j / N), as
+ * fhecore.ckks.Encoder) by the HEAAN / Lattigo special FFT in float64.  n = N/2, M = 2N,
+ * rot[j] = 5^j mod M, W[k] = (cos, sin)(pi k / N) computed as M_PI * (double)k / (double)N, every
+ * entry straight from libm (fhe_encode_roots returns the table the context uploads; it needs no
+ * device).  A complex product (dr, di)(wr, wi) is the four rounded products dr wr, di wi, dr wi,
+ * di wr and the two rounded sums p1 - p2, p3 + p4: no fused multiply-add, no reassociation.
+ * tests/encode_ref.py restates both directions; the results equal it bit for bit.
+ *
+ * fhe_encode: slots is device memory [count][N/2][2] doubles, interleaved (re, im).
+ *   v = z;  for len = n, n/2 .. 2 (lh = len/2, lq = 4 len), every block start i, j < lh:
+ *       w = W[(lq - rot[j] % lq) (M/lq)];  (v[i+j], v[i+j+lh]) = (a + b, (a - b) w)
+ *   v = v[bitrev_n];  s = delta / n;  c[k] = rint(Re v[k] s),  c[k + n] = rint(Im v[k] s)
+ *   (ties to even), and row r of out [count][level (+ K)][N] is NTT(c mod q_limb(r)), canonical
+ *   residues; the rows are the Q-limbs 0 .. level-1, then with special != 0 the P-limbs.
+ *   level = L with special is the [L + K][N] diagonal fhe_linear_transform / rotate_sum_hoisted
+ *   read in place at every level; special == 0 is the [level][N] plaintext of fhe_mul_plain_level
+ *   and fhe_encrypt.  Precondition (not checked): |c| < 2^62; for NaN, infinite or larger values
+ *   the residues are unspecified but canonical, and nothing faults.
+ * fhe_decode: pt is [count][pt_rows][N], NTT form; limb 0 is read, and limb 1 when level >= 2,
+ *   through the row stride pt_rows.  x_i = INTT_i(limb i); level 1: V = x_0 centred over q_0;
+ *   level >= 2: t = ((x_1 - x_0) q_0^-1) mod q_1, V = x_0 + q_0 t centred over q_0 q_1;
+ *   x = (double)V with one round-to-nearest-even;  v[k] = (x[k], x[k + n]);  v = v[bitrev_n];
+ *   for len = 2, 4 .. n:  w = W[(rot[j] % lq) (M/lq)];  b = v[i+j+lh] w;
+ *       (v[i+j], v[i+j+lh]) = (a + b, a - b);   slots = v / delta (IEEE division).
+ *   Precondition: the plaintext's true centred value is below q_0 q_1 / 2 (q_0 / 2 at level 1)
+ *   in magnitude, which holds for every plaintext whose scaled message fits two primes.
+ * FHE_EINVAL before any launch: a delta that is not finite and positive; a null context or
+ * pointer; level 0 or above L; special on a context with K = 0; pt_rows < min(level, 2); any
+ * overlap of out with slots (of slots with pt); workspace == NULL while the stream is capturing.
+ * count == 0 is a no-op.  Workspace: fhe_encode_workspace / fhe_decode_workspace(ctx, count) bytes
+ * (2 / 3 count N words); NULL = internal.  Capture-safe with an explicit workspace: nothing is
+ * allocated or synchronised.  FHECORE_ENCODE_UNFUSED=1 makes fhe_encode take the form of contexts
+ * with a modulus >= 2^61 (a separate lift, then whole NTTs) on any context: the same bits. */
+int fhe_encode_roots(uint32_t log_n, double* out /* [2N][2] = (cos, sin)(pi k / N) */);
+size_t fhe_encode_workspace(const fhe_ctx* ctx, uint32_t count);
+int fhe_encode(const fhe_ctx* ctx, uint64_t* out, const double* slots, double delta,
+               uint32_t level, int special, uint32_t count, void* workspace, fhe_stream_t stream);
+size_t fhe_decode_workspace(const fhe_ctx* ctx, uint32_t count);
+int fhe_decode(const fhe_ctx* ctx, double* slots, const uint64_t* pt, double delta,
+               uint32_t pt_rows, uint32_t level, uint32_t count, void* workspace,
+               fhe_stream_t stream);
 
 /* ---- HIP graphs: capture a sequence of libfhecore calls on `stream` and replay it -----------
  * Between fhe_graph_begin and fhe_graph_end every call that takes a workspace must be given an

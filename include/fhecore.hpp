@@ -493,6 +493,36 @@ class Evaluator {
     return out;
   }
 
+  // CKKS encode (fhe_encode): slots holds N/2 complex doubles, interleaved (re, im), one double
+  // per word of the buffer (N words) -> the 1-component NTT-form plaintext over the Q-limbs
+  // 0 .. level-1 (and, with special, the context's P-limbs after them): what mul_plain takes.
+  Ciphertext encode(const DeviceBuffer& slots, double delta, uint32_t level,
+                    bool special = false) const {
+    if (slots.size() != ctx_.n()) throw Error(FHE_EINVAL, "encode: need N/2 complex slots (N words)");
+    if (level == 0 || level > ctx_.L())
+      throw Error(FHE_EINVAL, "encode: level must be in [1, L]");
+    Ciphertext out(ctx_, 1, level + (special ? ctx_.K() : 0), true);
+    const size_t need = fhe_encode_workspace(ctx_.get(), 1);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    check(fhe_encode(ctx_.get(), out.data(), reinterpret_cast<const double*>(slots.data()), delta,
+                     level, special ? 1 : 0, 1, ws_.data(), s_),
+          "fhe_encode");
+    return out;
+  }
+  // CKKS decode (fhe_decode): a 1-component NTT-form plaintext carrying a value over `level`
+  // Q-limbs (limbs 0 and 1 are read) -> N/2 complex doubles, interleaved, in a buffer of N words.
+  DeviceBuffer decode(const Ciphertext& pt, double delta, uint32_t level) const {
+    if (pt.components != 1 || !pt.ntt_form)
+      throw Error(FHE_EINVAL, "decode: need a 1-component NTT-form plaintext");
+    DeviceBuffer out(ctx_.n());
+    const size_t need = fhe_decode_workspace(ctx_.get(), 1);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    check(fhe_decode(ctx_.get(), reinterpret_cast<double*>(out.data()), pt.data(), delta, pt.limbs,
+                     level, 1, ws_.data(), s_),
+          "fhe_decode");
+    return out;
+  }
+
  private:
   uint64_t* plain_ws() const {
     const size_t need = fhe_lincomb_workspace(ctx_.get(), 1);

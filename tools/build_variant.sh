@@ -16,7 +16,8 @@ if [ -n "$REV" ]; then
   src=$tmp/gpu-fhe_amd/csrc
 fi
 pids=()
-for f in host_tables.cpp context.cpp capi.cpp prof.cpp ntt.hip ntt_ks.hip elementwise.hip rns.hip galois.hip wire.cpp serialize.cpp pipeline.hip keygen.hip dist.cpp; do
+# every translation unit of that tree (the list grows with the library: plain.hip, encode.hip, ...)
+for f in $(cd $src && ls *.cpp *.hip); do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $defs -c $src/$f -o $out/$f.o &
   pids+=($!)
 done
