@@ -712,6 +712,44 @@ int fhe_mul_plain_level(const fhe_ctx* c, uint64_t* out, const uint64_t* ct, con
   return launch_mul_plain(c, out, ct, pt, pt_rows, pt_batch, level, batch, rescale != 0, ws, hs(s));
 }
 
+// the shared checks of fhe_conj_split_level / fhe_conj_merge_level: outs[] against ins[], all
+// [batch][2][level][N]
+static int conj_check(const fhe_ctx* c, uint64_t* const* outs, int nout, const uint64_t* const* ins,
+                      uint32_t level, uint32_t batch, const char* who) {
+  int rc = check_level(c, level, who);
+  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, who))) return rc;
+  for (int i = 0; i < nout; ++i)
+    if (!outs[i]) return (set_error(std::string(who) + ": null data pointer"), kInvalid);
+  if (!ins[0] || !ins[1]) return (set_error(std::string(who) + ": null data pointer"), kInvalid);
+  const uint64_t words = (uint64_t)batch * 2 * level * c->n;
+  for (int i = 0; i < nout; ++i)
+    for (int j = 0; j < 2; ++j)
+      if ((rc = check_plain_alias(outs[i], words, ins[j], words, true,
+                                  std::string(who) + ": an output overlaps an input")))
+        return rc;
+  if (nout == 2 && spans_overlap(outs[0], words, outs[1], words)) {
+    set_error(std::string(who) + ": re and im overlap");
+    return kInvalid;
+  }
+  return kOk;
+}
+
+int fhe_conj_split_level(const fhe_ctx* c, uint64_t* re, uint64_t* im, const uint64_t* ct,
+                         const uint64_t* cc, uint32_t level, uint32_t batch, fhe_stream_t s) {
+  uint64_t* outs[2] = {re, im};
+  const uint64_t* ins[2] = {ct, cc};
+  if (int rc = conj_check(c, outs, 2, ins, level, batch, "fhe_conj_split_level")) return rc;
+  return launch_conj(c, false, re, im, ct, cc, level, batch, hs(s));
+}
+
+int fhe_conj_merge_level(const fhe_ctx* c, uint64_t* out, const uint64_t* a, const uint64_t* b,
+                         uint32_t level, uint32_t batch, fhe_stream_t s) {
+  uint64_t* outs[1] = {out};
+  const uint64_t* ins[2] = {a, b};
+  if (int rc = conj_check(c, outs, 1, ins, level, batch, "fhe_conj_merge_level")) return rc;
+  return launch_conj(c, true, out, nullptr, a, b, level, batch, hs(s));
+}
+
 size_t fhe_mod_raise_workspace(const fhe_ctx* c, uint32_t batch) {
   return c ? mod_raise_workspace_bytes(c, batch) : 0;
 }

@@ -114,6 +114,10 @@ int ctx_create(fhe_ctx** out, u32 log_n, const u64* q, u32 L, const u64* p, u32 
     const Pair64 inv = shoup_pair(powmod_u64(mods[0] % mods[1], mods[1] - 2, mods[1]), mods[1]);
     c->enc_q0inv = make_ulonglong2(inv.x, inv.y);
   }
+  // conj_split / conj_merge (plain.hip): X^(N/2) in NTT form is psi^(N/2) on the first half of a
+  // row and its negative on the second
+  std::vector<Pair64> conjw(L);
+  for (size_t i = 0; i < L; ++i) conjw[i] = shoup_pair(powmod_u64(c->psi[i], n / 2, mods[i]), mods[i]);
   int rc = kOk;
   if ((rc = upload(&c->d_mods, c->mods_host.data(), M)) ||
       (rc = upload(&c->d_tw_fwd, reinterpret_cast<const ulonglong2*>(twf.data()), M * n)) ||
@@ -123,6 +127,7 @@ int ctx_create(fhe_ctx** out, u32 log_n, const u64* q, u32 L, const u64* p, u32 
                               (size_t)L * n))) ||
       (rc = upload(&c->d_enc_roots, reinterpret_cast<const double2*>(roots.data()), 2 * n)) ||
       (rc = upload(&c->d_enc_rot, rot.data(), n / 2)) ||
+      (rc = upload(&c->d_conj_w, reinterpret_cast<const ulonglong2*>(conjw.data()), L)) ||
       (rc = build_rns_tables(c)) ||
       (rc = build_galois_tables(c))) {
     ctx_destroy(c);
@@ -144,6 +149,7 @@ int ctx_destroy(fhe_ctx* c) {
                     (void*)c->d_rs_half, (void*)c->d_lvl_inv, (void*)c->d_lvl_hat,
                     (void*)c->d_lvl_hat_w, (void*)c->d_lvl_hat_rw, (void*)c->d_lvl_hat_rwp,
                     (void*)c->d_lvl_nfold_up, (void*)c->d_enc_roots, (void*)c->d_enc_rot,
+                    (void*)c->d_conj_w,
                     c->workspace})
     if (ptr) (void)hipFree(ptr);
   delete c;

@@ -124,6 +124,9 @@ struct fhe_ctx {
   double2* d_enc_roots = nullptr;
   uint32_t* d_enc_rot = nullptr;
   ulonglong2 enc_q0inv = {0, 0};
+  // conj_split / conj_merge (plain.hip): [L] Shoup pairs of w_j = psi_j^(N/2), the value of
+  // X^(N/2) at NTT slots k < N/2 (q_j - w_j at k >= N/2)
+  ulonglong2* d_conj_w = nullptr;
 
   void* workspace = nullptr;
   size_t workspace_bytes = 0;
@@ -331,6 +334,10 @@ int launch_lincomb(const fhe_ctx* c, u64* out, const u64* const* cts, const u32*
 int launch_mul_plain(const fhe_ctx* c, u64* out, const u64* ct, const u64* pt, u32 pt_rows,
                      u32 pt_batch, u32 level, u32 batch, bool rescale, void* ws, hipStream_t s);
 size_t lincomb_workspace_bytes(const fhe_ctx* c, u32 batch);
+// re = ct + cc, im = -X^(N/2) (ct - cc) (split), or out = a + X^(N/2) b (merge: re = out, ct = a,
+// cc = b, im unused), all [batch][2][level][N] NTT form, one pass
+int launch_conj(const fhe_ctx* c, bool merge, u64* re, u64* im, const u64* ct, const u64* cc,
+                u32 level, u32 batch, hipStream_t s);
 
 // ---- launchers (rns.hip) --------------------------------------------------------------
 // Per-rank body of the hybrid key-switch (SURVEY.md §8a', §8e) over `batch` ciphertexts sharing

@@ -7,6 +7,8 @@
 // and no generator state lives on the device.
 //   uniform mod q   floor(r q / 2^128) of a 128-bit draw (bias < 2^-67 for q < 2^61)
 //   ternary         (r mod 3) - 1 of a 32-bit draw, the same integer on every limb
+//   sparse ternary  exactly h coefficients +-1: the h smallest 64-bit keys (r.x << 32) | c
+//                   (fhe_keygen_secret_sparse; restated by tests/sparse_ref.py)
 //   error           centred binomial, eta = 21 (sd ~3.2): popcount of 21 bits minus 21 bits
 // Keys and ciphertexts are NTT form over their limbs (the layout of the rest of the library).
 #include "../../include/fhecore.h"
@@ -114,8 +116,66 @@ int mac_s(const fhe_ctx* c, u64* out, u64 pout, const u64* x, u64 px, const u64*
 }
 
 // stream tags: which draw a sample belongs to (same seed, disjoint counters)
-enum Tag : u32 { kTagSecret = 1, kTagPkA = 2, kTagPkE = 3, kTagKsA = 0x100, kTagKsE = 0x101,
-                 kTagEncU = 32, kTagEncE0 = 33, kTagEncE1 = 34, kTagEncA = 35, kTagEncE = 36 };
+enum Tag : u32 { kTagSecret = 1, kTagPkA = 2, kTagPkE = 3, kTagSparse = 4, kTagKsA = 0x100,
+                 kTagKsE = 0x101, kTagEncU = 32, kTagEncE0 = 33, kTagEncE1 = 34, kTagEncA = 35,
+                 kTagEncE = 36 };
+
+// ---- fixed-Hamming-weight secret (fhe_keygen_secret_sparse) --------------------------------------
+// Coefficient c draws r = philox(c, 0xffffffff, 0, kTagSparse) and carries the 64-bit key
+// (r.x << 32) | c: distinct keys, so "the h smallest keys" is one set whatever the order of
+// evaluation.  One workgroup finds the h-th smallest key T by a radix select, 8 bits a pass from
+// the top: a pass histograms the digit of every key that matches the prefix found so far (the
+// draw is regenerated, nothing is stored), then every lane walks the 256 counts to the digit that
+// holds rank h.  N <= 2^17: 8 passes of at most 128 draws per lane.  Coefficient c is then
+// nonzero iff key_c <= T, +1 if (r.y & 1) == 0, else -1; the integer goes to `row` (the LAST limb's
+// row, as a residue of q_last), which k_sparse_spread reads and never writes.
+constexpr int kSelThreads = 1024;
+
+__device__ __forceinline__ u64 sparse_key(u32 c, u32 seed_lo, u32 seed_hi, u32* sign) {
+  const P4 r = philox4x32_10(P4{c, 0xffffffffu, 0, kTagSparse}, seed_lo, seed_hi);
+  *sign = r.y & 1;
+  return ((u64)r.x << 32) | c;
+}
+
+__global__ __launch_bounds__(kSelThreads) void k_sparse_select(u64* __restrict__ row, u32 n, u32 h,
+                                                              u32 seed_lo, u32 seed_hi,
+                                                              u64 q_last) {
+  __shared__ u32 hist[256];
+  u64 prefix = 0, mask = 0;
+  u32 rank = h;  // 1-based rank of T among the keys matching (prefix, mask)
+  u32 sign;
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (u32 c = threadIdx.x; c < n; c += kSelThreads) {
+      const u64 key = sparse_key(c, seed_lo, seed_hi, &sign);
+      if ((key & mask) == prefix) atomicAdd(&hist[(u32)(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    u32 d = 0, below = 0;  // every lane walks the same counts: no broadcast needed
+    while (d < 255 && below + hist[d] < rank) below += hist[d++];
+    rank -= below;
+    prefix |= (u64)d << shift;
+    mask |= 255ull << shift;
+    __syncthreads();  // the next pass clears hist
+  }
+  for (u32 c = threadIdx.x; c < n; c += kSelThreads) {
+    const u64 key = sparse_key(c, seed_lo, seed_hi, &sign);
+    row[c] = key <= prefix ? (sign ? q_last - 1 : 1) : 0;
+  }
+}
+
+// rows 0 .. nlimbs-1 of sk [nlimbs + 1][N] from the last row's integer (0, 1 or q_last - 1).
+// Grid: x over coefficients, y = limb.
+__global__ __launch_bounds__(kThreads) void k_sparse_spread(u64* __restrict__ sk, u32 log_n,
+                                                            u32 nlimbs,
+                                                            const ModParams* __restrict__ mods) {
+  const u64 n = 1ull << log_n;
+  const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 l = blockIdx.y;
+  const u64 v = sk[(u64)nlimbs * n + c];
+  sk[(u64)l * n + c] = v <= 1 ? v : mods[l].q - 1;
+}
 
 }  // namespace
 }  // namespace fhe
@@ -140,6 +200,25 @@ int fhe_keygen_secret(const fhe_ctx* c, uint64_t* sk, uint64_t seed, fhe_stream_
   const u32 M = (u32)c->moduli.size();
   int rc;
   if ((rc = sample(c, sk, (u64)M * c->n, 1, 0, M, kTernary, seed, kTagSecret, s))) return rc;
+  return launch_ntt(c, true, sk, sk, 1, (u64)M * c->n, 0, M, s);
+}
+
+int fhe_keygen_secret_sparse(const fhe_ctx* c, uint64_t* sk, uint32_t h, uint64_t seed,
+                             fhe_stream_t st) {
+  if (!c || !sk) return (set_error("fhe_keygen_secret_sparse: null context or output"), kInvalid);
+  if (h == 0 || h > c->n)
+    return (set_error("fhe_keygen_secret_sparse: the Hamming weight must be in [1, N]"), kInvalid);
+  const hipStream_t s = static_cast<hipStream_t>(st);
+  const u32 M = (u32)c->moduli.size();
+  if (int rc = check_grid(c->n / kThreads, kThreads, M, 1, "keygen_secret_sparse")) return rc;
+  k_sparse_select<<<1, kSelThreads, 0, s>>>(sk + (u64)(M - 1) * c->n, (u32)c->n, h, (u32)seed,
+                                            (u32)(seed >> 32), c->moduli[M - 1]);
+  FHE_HIP_CHECK(hipGetLastError());
+  if (M > 1) {
+    k_sparse_spread<<<dim3((u32)(c->n / kThreads), M - 1), kThreads, 0, s>>>(sk, c->log_n, M - 1,
+                                                                            c->d_mods);
+    FHE_HIP_CHECK(hipGetLastError());
+  }
   return launch_ntt(c, true, sk, sk, 1, (u64)M * c->n, 0, M, s);
 }
 

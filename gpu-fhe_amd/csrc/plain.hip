@@ -127,7 +127,71 @@ int finish(const fhe_ctx* c, int mode, u64* out, LincombArgs& a, u32 batch, u32 
   return launch_rescale(c, out, sum, 2 * batch, level, true, sum + (u64)batch * 2 * c->L * c->n, s);
 }
 
+// conj_split / conj_merge (fhe_conj_split_level / fhe_conj_merge_level).  X^(N/2) multiplies every
+// slot by i and is, in NTT layout, the constant w_l = psi_l^(N/2) at elements k < N/2 of limb l
+// and q_l - w_l at k >= N/2 (element k evaluates at psi^(2 brv(k) + 1), and brv(k) is odd exactly
+// when the top bit of k is set), so the side is uniform over a workgroup's pairs.
+//   split: re = x + y, im = -X^(N/2) (x - y) = w (y - x) | w (x - y)   (first | second half)
+//   merge: re = x + X^(N/2) y              = x + w y   | x - w y
+// The product by w is the exact-quotient Shoup form, [0, 2q) with 2q < 2^64 for every context
+// modulus (wide ones included), then one conditional subtraction: canonical in and out.  The
+// pointers may alias element for element (an output that is an input), so none is __restrict__
+// and every element is read before it is written by the one lane that owns it.
+template <bool MERGE>
+__global__ __launch_bounds__(kLcThreads) void k_conj(u64* re, u64* im, const u64* x, const u64* y,
+                                                    u32 level, u32 row_pairs, u32 nrows,
+                                                    const ulonglong2* __restrict__ wtab,
+                                                    const ModParams* __restrict__ mods) {
+  const u32 i = blockIdx.x * kLcThreads + threadIdx.x;
+  if (i >= row_pairs) return;
+  const bool second = i >= row_pairs / 2;
+  for (u32 row = blockIdx.y; row < nrows; row += gridDim.y) {
+    const u32 l = row % level;
+    const u64 q = mods[l].q;
+    const ulonglong2 w = wtab[l];
+    const u64 at = (u64)row * row_pairs + i;
+    const vu64x2 a = __builtin_nontemporal_load(reinterpret_cast<const vu64x2*>(x) + at);
+    const vu64x2 b = __builtin_nontemporal_load(reinterpret_cast<const vu64x2*>(y) + at);
+    vu64x2 r0, r1;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const u64 u = e ? a.y : a.x, v = e ? b.y : b.x;
+      u64 o0, o1 = 0;
+      if constexpr (MERGE) {
+        const u64 t = csub(shoup_lazy(v, w.x, w.y, q), q);
+        o0 = second ? (u >= t ? u - t : u + (q - t)) : csub(u + t, q);
+      } else {
+        o0 = csub(u + v, q);
+        const u64 d = second ? (u >= v ? u - v : u + (q - v)) : (v >= u ? v - u : v + (q - u));
+        o1 = csub(shoup_lazy(d, w.x, w.y, q), q);
+      }
+      if (e) r0.y = o0, r1.y = o1; else r0.x = o0, r1.x = o1;
+    }
+    __builtin_nontemporal_store(r0, reinterpret_cast<vu64x2*>(re) + at);
+    if constexpr (!MERGE) __builtin_nontemporal_store(r1, reinterpret_cast<vu64x2*>(im) + at);
+  }
+}
+
 }  // namespace
+
+int launch_conj(const fhe_ctx* c, bool merge, u64* re, u64* im, const u64* ct, const u64* cc,
+                u32 level, u32 batch, hipStream_t s) {
+  const u64 rows64 = (u64)batch * 2 * level;
+  if (rows64 == 0) return kOk;
+  if (rows64 > 0xffffffffull) {
+    set_error("conj_split / conj_merge: too many poly-limb rows");
+    return kInvalid;
+  }
+  const u32 nrows = (u32)rows64, row_pairs = (u32)(c->n / 2);  // N >= 2^10: whole pairs per row
+  const dim3 g((row_pairs + kLcThreads - 1) / kLcThreads, nrows < 65535 ? nrows : 65535);
+  if (merge)
+    k_conj<true><<<g, kLcThreads, 0, s>>>(re, im, ct, cc, level, row_pairs, nrows, c->d_conj_w, c->d_mods);
+  else
+    k_conj<false><<<g, kLcThreads, 0, s>>>(re, im, ct, cc, level, row_pairs, nrows, c->d_conj_w, c->d_mods);
+  FHE_HIP_CHECK(hipGetLastError());
+  prof_mark(s, merge ? "conj_merge" : "conj_split");
+  return kOk;
+}
 
 size_t lincomb_workspace_bytes(const fhe_ctx* c, u32 batch) {
   return (size_t)batch * 2 * c->L * c->n * sizeof(u64) + rescale_workspace_bytes(c, 2 * batch, c->L);

@@ -116,6 +116,9 @@ SIGNATURES = {
     "fhe_graph_destroy": (_i32, [_vp]),
     "fhe_sample": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _u64, _u32, _vp]),
     "fhe_keygen_secret": (_i32, [_vp, _vp, _u64, _vp]),
+    "fhe_keygen_secret_sparse": (_i32, [_vp, _vp, _u32, _u64, _vp]),
+    "fhe_conj_split_level": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
+    "fhe_conj_merge_level": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "fhe_keygen_public": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "fhe_keygen_switch": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "fhe_encrypt": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),

@@ -596,12 +596,21 @@ class Context:
                                     seed, tag, _stream(out)), "fhe_sample")
         return out
 
-    def keygen_secret(self, seed=None):
-        """Ternary secret, NTT form over all L + K limbs: [L + K, N]."""
+    def keygen_secret(self, seed=None, hamming_weight=None):
+        """Ternary secret, NTT form over all L + K limbs: [L + K, N].  hamming_weight = h: exactly
+        h coefficients are +-1 (fhe_keygen_secret_sparse; the secret of fhecore.bootstrap)."""
         seed = _nonce(seed)
         sk = _empty(self.L + self.K, self.n, dtype=torch.int64, device=self._dev())
         with torch.cuda.device(self.device):
-            check(load().fhe_keygen_secret(self._ptr, _ptr(sk), seed, _stream(sk)), "fhe_keygen_secret")
+            if hamming_weight is None:
+                check(load().fhe_keygen_secret(self._ptr, _ptr(sk), seed, _stream(sk)),
+                      "fhe_keygen_secret")
+            else:
+                h = int(hamming_weight)
+                if not 0 <= h < 1 << 32:  # (the range [1, N] is fhe_keygen_secret_sparse's check)
+                    raise ValueError("keygen_secret: hamming_weight out of range")
+                check(load().fhe_keygen_secret_sparse(self._ptr, _ptr(sk), h, seed, _stream(sk)),
+                      "fhe_keygen_secret_sparse")
         return sk
 
     def keygen_public(self, sk, seed=None):
@@ -779,6 +788,40 @@ class Context:
         if getattr(self, "_one", None) is None:
             self._one = self.encode_scalars([1], exact=True)
         return self.lincomb([ct], self._one, level=level, out=out)
+
+    # ---- real / imaginary split and merge (fhe_conj_split_level / fhe_conj_merge_level) --------
+    def _conj_pair(self, a, b, who):
+        lv = self._ct_level(a, who)
+        _check_tensor(b, f"{who}: second operand", (self.n,))
+        if b.shape != a.shape or b.device != a.device:
+            raise ValueError(f"{who}: both operands must be [..., 2, l, N] of one shape on one device")
+        return lv, a.numel() // (2 * lv * self.n)
+
+    def conj_split(self, ct, cc, out=None):
+        """ct [..., 2, l, N] NTT form and its conjugate cc (rotate by Galois element 2N - 1) ->
+        (re, im) = (ct + cc, -X^(N/2) (ct - cc)), whose slots are 2 Re z and 2 Im z: one pass,
+        exact, no level consumed.  out = (re, im): caller-provided outputs, each of which may be
+        ct or cc itself; no workspace."""
+        lv, batch = self._conj_pair(ct, cc, "conj_split")
+        if out is None:
+            re, im = _empty_like(ct), _empty_like(ct)
+        else:
+            re = _check_out(out[0], ct, ct.shape, "conj_split: re")
+            im = _check_out(out[1], ct, ct.shape, "conj_split: im")
+        with torch.cuda.device(self.device):
+            check(load().fhe_conj_split_level(self._ptr, _ptr(re), _ptr(im), _ptr(ct), _ptr(cc), lv,
+                                              batch, _stream(ct)), "fhe_conj_split_level")
+        return re, im
+
+    def conj_merge(self, a, b, out=None):
+        """a + X^(N/2) b for a, b [..., 2, l, N] NTT form: slots a_j + i b_j, one pass, exact.
+        out may be a or b itself; no workspace."""
+        lv, batch = self._conj_pair(a, b, "conj_merge")
+        out = _empty_like(a) if out is None else _check_out(out, a, a.shape, "conj_merge: out")
+        with torch.cuda.device(self.device):
+            check(load().fhe_conj_merge_level(self._ptr, _ptr(out), _ptr(a), _ptr(b), lv, batch,
+                                              _stream(a)), "fhe_conj_merge_level")
+        return out
 
     # ---- ModRaise (fhe_mod_raise): from the bottom of the chain back up ---------------------
     def mod_raise(self, ct, level=None, workspace=None, out=None):

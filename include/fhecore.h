@@ -456,6 +456,16 @@ int fhe_deserialize(const fhe_ctx* ctx, const void* host_buf, size_t size, uint6
 int fhe_sample(const fhe_ctx* ctx, uint64_t* out, uint32_t polys, uint32_t limb0,
                uint32_t nlimbs, int kind, uint64_t seed, uint32_t tag, fhe_stream_t stream);
 int fhe_keygen_secret(const fhe_ctx* ctx, uint64_t* sk, uint64_t seed, fhe_stream_t stream);
+/* fhe_keygen_secret_sparse: a secret of fixed Hamming weight h (CKKS bootstrapping: ModRaise's
+ * integer polynomial obeys |I| <= (h + 2) / 2), sk [L + K][N] NTT form as fhe_keygen_secret.
+ * Coefficient c draws r = philox4x32_10({c, 0xffffffff, 0, tag 4}, seed) and carries the 64-bit key
+ * (r.x << 32) | c (distinct by construction); the h coefficients with the smallest keys are
+ * nonzero, +1 if (r.y & 1) == 0, else -1, the same integer on every limb.  The definition does not
+ * depend on the order of evaluation (one workgroup selects the h-th smallest key by a radix select
+ * that regenerates the draws: no workspace).  FHE_EINVAL before any launch: a null context or
+ * pointer, h == 0 or h > N. */
+int fhe_keygen_secret_sparse(const fhe_ctx* ctx, uint64_t* sk, uint32_t h, uint64_t seed,
+                             fhe_stream_t stream);
 int fhe_keygen_public(const fhe_ctx* ctx, uint64_t* pk, const uint64_t* sk, uint64_t seed,
                       fhe_stream_t stream);
 int fhe_keygen_switch(const fhe_ctx* ctx, uint64_t* key, const uint64_t* sk,
@@ -517,6 +527,26 @@ int fhe_lincomb_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* const* 
 int fhe_mul_plain_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* ct, const uint64_t* pt,
                         uint32_t pt_rows, uint32_t pt_batch, uint32_t level, uint32_t batch,
                         int rescale, void* workspace, fhe_stream_t stream);
+
+/* ---- real / imaginary split and merge of the slots (CKKS bootstrapping) -----------------------
+ * X^(N/2) multiplies every slot by i: slot j sits at the root exp(i pi 5^j / N) and 5^j = 1 mod 4.
+ * In NTT layout it is the constant w_j = psi_j^(N/2) at elements k < N/2 of limb j and q_j - w_j at
+ * k >= N/2, so the product is exact and costs no level.  All operands are [batch][2][l][N], NTT
+ * form, `level` = l live Q-limbs, canonical residues in and out.
+ * fhe_conj_split_level: ct a ciphertext and cc its conjugate (fhe_rotate_level with Galois element
+ * 2N - 1);  re = ct + cc,  im = -X^(N/2) (ct - cc):  the slots of re / im are 2 Re z / 2 Im z.
+ * fhe_conj_merge_level: out = a + X^(N/2) b  (slots a_j + i b_j).
+ * One pass each: two ciphertexts read, two (split) or one (merge) written; the composed forms
+ * (fhe_lincomb_level twice and fhe_mul_plain_level by a plaintext of +-w; fhe_mul_plain_level and
+ * fhe_lincomb_level) take four and two.
+ * FHE_EINVAL before any launch: a null context or pointer; level == 0 or level > L.
+ * Aliasing: an output may be an input itself (same start pointer: the operation is elementwise);
+ * any other overlap of an output with an input, or of re with im, is FHE_EINVAL.
+ * No workspace; capture-safe: nothing is allocated or synchronised. */
+int fhe_conj_split_level(const fhe_ctx* ctx, uint64_t* re, uint64_t* im, const uint64_t* ct,
+                         const uint64_t* cc, uint32_t level, uint32_t batch, fhe_stream_t stream);
+int fhe_conj_merge_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* a, const uint64_t* b,
+                         uint32_t level, uint32_t batch, fhe_stream_t stream);
 
 /* ---- ModRaise: from the bottom of the modulus chain back up (CKKS bootstrapping) ------------
  * in is [batch][2][in_level][N], NTT form, canonical residues; only limb 0 of each polynomial is

@@ -6,6 +6,8 @@
 // [components][limbs][N] uint64 device arrays, and an Evaluator whose methods map 1:1 to the
 // C entry points (include/fhecore.h).  Errors become fhe::Error exceptions carrying
 // fhe_last_error().  Requires the HIP runtime (hipMalloc/hipMemcpy) and -lfhecore.
+// The polynomial evaluation (fhecore.polyeval) and the bootstrap composed from these calls
+// (fhecore.bootstrap.Bootstrapper) are Python-level: they have no entry here or in fhecore.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -131,6 +133,13 @@ class KeyGenerator {
       : ctx_(ctx), s_(stream) {
     sk_.s = DeviceBuffer((size_t)(ctx.L() + ctx.K()) * ctx.n());
     check(fhe_keygen_secret(ctx.get(), sk_.s.data(), seed, s_), "fhe_keygen_secret");
+  }
+  // a secret of fixed Hamming weight (fhe_keygen_secret_sparse: CKKS bootstrapping)
+  KeyGenerator(const Context& ctx, uint64_t seed, uint32_t hamming_weight, hipStream_t stream)
+      : ctx_(ctx), s_(stream) {
+    sk_.s = DeviceBuffer((size_t)(ctx.L() + ctx.K()) * ctx.n());
+    check(fhe_keygen_secret_sparse(ctx.get(), sk_.s.data(), hamming_weight, seed, s_),
+          "fhe_keygen_secret_sparse");
   }
   const SecretKey& secret() const { return sk_; }
   PublicKey public_key(uint64_t seed) const {
@@ -490,6 +499,29 @@ class Evaluator {
     if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
     check(fhe_mod_raise(ctx_.get(), out.data(), ct.data(), ct.limbs, out_level, 1, ws_.data(), s_),
           "fhe_mod_raise");
+    return out;
+  }
+  // Real / imaginary split (fhe_conj_split_level): ct and its conjugate cc (rotate by Galois
+  // element 2N - 1) at one level -> (re, im) = (ct + cc, -X^(N/2) (ct - cc)), whose slots are
+  // 2 Re z and 2 Im z; exact, no level consumed.
+  std::pair<Ciphertext, Ciphertext> conj_split(const Ciphertext& ct, const Ciphertext& cc) const {
+    same(ct, cc, "conj_split");
+    if (ct.components != 2 || !ct.ntt_form)
+      throw Error(FHE_EINVAL, "conj_split: need 2-component NTT-form ciphertexts");
+    Ciphertext re(ctx_, 2, ct.limbs, true), im(ctx_, 2, ct.limbs, true);
+    check(fhe_conj_split_level(ctx_.get(), re.data(), im.data(), ct.data(), cc.data(), ct.limbs, 1,
+                               s_),
+          "fhe_conj_split_level");
+    return {std::move(re), std::move(im)};
+  }
+  // a + X^(N/2) b (fhe_conj_merge_level): slots a_j + i b_j.
+  Ciphertext conj_merge(const Ciphertext& a, const Ciphertext& b) const {
+    same(a, b, "conj_merge");
+    if (a.components != 2 || !a.ntt_form)
+      throw Error(FHE_EINVAL, "conj_merge: need 2-component NTT-form ciphertexts");
+    Ciphertext out(ctx_, 2, a.limbs, true);
+    check(fhe_conj_merge_level(ctx_.get(), out.data(), a.data(), b.data(), a.limbs, 1, s_),
+          "fhe_conj_merge_level");
     return out;
   }
 
