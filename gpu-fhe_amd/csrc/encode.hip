@@ -181,11 +181,6 @@ int launch_sfft(const fhe_ctx* c, const void* in, void* out, double2* work, doub
   return launch_pass<ENC>(second, count, s);
 }
 
-// row r of an encoded plaintext -> context limb: the Q-limbs 0 .. level-1, then the P-limbs
-__device__ __forceinline__ u32 enc_limb(u32 r, u32 level, u32 L) {
-  return r < level ? r : L + (r - level);
-}
-
 // The unfused lift (wide contexts): coefficients [count][N] -> out [count][rows][N], canonical
 // residues of every row's limb, to be NTT'd in place.  Grid y = row, z = plaintext.
 __global__ __launch_bounds__(kFftThreads) void k_encode_spread(u64* __restrict__ out,
@@ -198,10 +193,7 @@ __global__ __launch_bounds__(kFftThreads) void k_encode_spread(u64* __restrict__
   const u32 r = blockIdx.y;
   const u64 p = blockIdx.z;
   const ModParams m = mods[enc_limb(r, level, L)];
-  const long long v = cf[p * n + i];
-  const u64 mag = v < 0 ? 0 - (u64)v : (u64)v;
-  const u64 res = reduce_word(mag, m);
-  out[(p * rows + r) * n + i] = (v < 0 && res != 0) ? m.q - res : res;
+  out[(p * rows + r) * n + i] = lift_signed((u64)cf[p * n + i], m);
 }
 
 // Decode's centring: x [count][nl][N] = INTT of limb 0 (and limb 1 when nl == 2) -> the centred
@@ -271,7 +263,7 @@ int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta,
   prof_mark(s, "encode_fft");
   const u64 ps = (u64)rows * n;
   if (!c->wide && !unfused) {
-    // the lift rides on the column-forward pass (ntt.hip k_encode_col); the row pass runs in place
+    // the lift rides on the column-forward pass (ntt.hip k_lift_col); the row pass runs in place
     if ((rc = launch_encode_col(c, reinterpret_cast<const u64*>(cf), out, count, level, rows, s)))
       return rc;
     if ((rc = launch_ntt_row_fwd_r2(c, out, ps, out, ps, count, 0, level, s))) return rc;

@@ -62,9 +62,7 @@ __global__ __launch_bounds__(kThreads) void k_rescale_coeff(u64* __restrict__ ou
   const u32 i = blockIdx.y;
   const u64 p = blockIdx.z;
   const ModParams ml = mods[nl - 1], mi = mods[i];
-  const u64 h = ml.q >> 1;
-  const u64 t = csub(in[(p * nl + nl - 1) * n + c] + h, ml.q);
-  const u64 tmp = csub(reduce_word(t, mi) + mi.q - half[i], mi.q);
+  const u64 tmp = lift_centred(in[(p * nl + nl - 1) * n + c], ml.q, mi.q - half[i], mi);
   const u64 d = in[(p * nl + i) * n + c] + mi.q - tmp;
   const ulonglong2 w = tab[i];
   out[(p * (nl - 1) + i) * n + c] = csub(shoup_lazy(d, w.x, w.y, mi.q), mi.q);
@@ -82,8 +80,7 @@ __global__ __launch_bounds__(kThreads) void k_rescale_spread(u64* __restrict__ t
   const u32 i = blockIdx.y;
   const u64 p = blockIdx.z;
   const ModParams ml = mods[nl - 1], mi = mods[i];
-  const u64 t = csub(last[p * n + c] + (ml.q >> 1), ml.q);
-  tmp[(p * (nl - 1) + i) * n + c] = csub(reduce_word(t, mi) + mi.q - half[i], mi.q);
+  tmp[(p * (nl - 1) + i) * n + c] = lift_centred(last[p * n + c], ml.q, mi.q - half[i], mi);
 }
 
 // Rescale, NTT form, step 2: out_i = (x_i - tmp_i) q_last^-1 mod q_i.
@@ -115,9 +112,8 @@ __global__ __launch_bounds__(kThreads) void k_modraise_spread(u64* __restrict__ 
   const u32 i = blockIdx.y + 1;
   const u64 p = blockIdx.z;
   const ModParams m0 = mods[0], mi = mods[i];
-  const u64 h = m0.q >> 1;
-  const u64 t = csub(x0[p * n + c] + h, m0.q);
-  out[(p * nl + i) * n + c] = csub(reduce_word(t, mi) + mi.q - reduce_word(h, mi), mi.q);
+  const u64 mh = mi.q - reduce_word(m0.q >> 1, mi);
+  out[(p * nl + i) * n + c] = lift_centred(x0[p * n + c], m0.q, mh, mi);
 }
 
 inline u64 modinv_u64(u64 a, u64 q) { return powmod_u64(a % q, q - 2, q); }
@@ -378,7 +374,7 @@ int launch_rescale(const fhe_ctx* c, u64* out, const u64* in, u32 polys, u32 nl,
                                 nl - 1, 1, s)))
     return rc;
   if (!c->wide) {
-    // the spread rides on the column-forward pass (k_rescale_col) and the finish on the row-forward
+    // the spread rides on the column-forward pass (ntt.hip k_lift_col) and the finish on the row-forward
     // pass (k_moddown_row with one half and the q_last^-1 table): out_i = (x_i - NTT(tmp)_i)
     // q_last^-1 straight from registers; tmp exists only column-passed
     const u64 sn = (u64)(nl - 1) * n;
@@ -417,7 +413,7 @@ int launch_mod_raise(const fhe_ctx* c, u64* out, const u64* in, u32 in_level, u3
     u64* x0 = static_cast<u64*>(ws);  // [polys][N]
     if ((rc = launch_ntt_strided(c, false, in, in_ps, x0, n, polys, 0, 1, s))) return rc;
     if (!c->wide && !unfused) {
-      // the lift rides on the column-forward pass (k_modraise_col); the row pass runs in place
+      // the lift rides on the column-forward pass (ntt.hip k_lift_col); the row pass runs in place
       if ((rc = launch_modraise_col(c, x0, out, polys, out_level, s))) return rc;
       if ((rc = launch_ntt_row_fwd_r2(c, out + n, out_ps, out + n, out_ps, polys, 1, out_level - 1,
                                       s)))

@@ -286,18 +286,19 @@ struct ModDownRowArgs {
   const ulonglong2* pinv = nullptr;  // per-limb Shoup pairs of the divisor's inverse; null: P^-1
 };
 int launch_moddown_row(const fhe_ctx* c, const ModDownRowArgs& a, hipStream_t s);
-// NTT-form rescale, spread + column-forward pass in one (ntt.hip, k_rescale_col): last [polys][N]
+// The three lifts that ride on the column-forward pass: one kernel (ntt.hip, k_lift_col) with one
+// policy struct each (RescaleLift, ModRaiseLift, EncodeLift, next to the kernel).
+// NTT-form rescale, spread + column-forward pass in one: last [polys][N]
 // (coefficient form of limb nq) -> dst [polys][nq][N] column-passed; half = rescale half table.
 int launch_rescale_col(const fhe_ctx* c, const u64* last, u64* dst, u32 polys, u32 nq,
                        const u64* half, hipStream_t s);
-// ModRaise, lift + column-forward pass in one (ntt.hip, k_modraise_col): x [polys][N] (coefficient
-// form of limb 0) -> limbs 1 .. out_level-1 of dst [polys][out_level][N] column-passed (schedule
+// ModRaise, lift + column-forward pass in one: x [polys][N] (coefficient form of limb 0) -> limbs 1 .. out_level-1 of dst [polys][out_level][N] column-passed (schedule
 // from 2: launch_ntt_row_fwd_r2 finishes them); limb 0 of dst is not touched.
 int launch_modraise_col(const fhe_ctx* c, const u64* x, u64* dst, u32 polys, u32 out_level,
                         hipStream_t s);
-// Encode, lift + column-forward pass in one (ntt.hip, k_encode_col): cf [polys][N] signed 64-bit
+// Encode, lift + column-forward pass in one: cf [polys][N] signed 64-bit
 // coefficients (|c| < 2^62) -> every row of dst [polys][rows][N] column-passed (schedule from 2:
-// launch_ntt_row_fwd_r2 finishes them); row r is limb r < level ? r : L + r - level.
+// launch_ntt_row_fwd_r2 finishes them); row r is limb enc_limb(r, level, L) (modarith.hpp).
 int launch_encode_col(const fhe_ctx* c, const u64* cf, u64* dst, u32 polys, u32 level, u32 rows,
                       hipStream_t s);
 // Fused ct x ct tensor: a, b [batch][2][nlimbs][N] coefficient form -> d [batch][3][nlimbs][N].

@@ -379,6 +379,31 @@ __device__ __forceinline__ u64 reduce_word(u64 t, const ModParams& m) {
   return csub(r, m.q);
 }
 
+// ---- lifts of one residue or coefficient into another limb -----------------------------------
+// Written once for the fused form (ntt.hip k_lift_col, the lift on the column-forward pass) and
+// the unfused one (the spread kernels of galois.hip and encode.hip, the path of wide contexts).
+
+// Centred lift of x in [0, q_from) into limb m: ((x + h) mod q_from - h) mod q, h = q_from / 2,
+// given mh = q - (h mod q) (rescale reads h mod q from its table, ModRaise reduces h once per
+// workgroup).  q may be far below q_from, so the centred word goes through reduce_word.
+__device__ __forceinline__ u64 lift_centred(u64 x, u64 q_from, u64 mh, const ModParams& m) {
+  const u64 h = q_from >> 1;
+  return csub(reduce_word(csub(x + h, q_from), m) + mh, m.q);
+}
+
+// Signed lift of a two's-complement word c into limb m: c mod q (|c| through reduce_word, negated
+// for c < 0, q itself folded to 0).
+__device__ __forceinline__ u64 lift_signed(u64 c, const ModParams& m) {
+  const bool neg = (int64_t)c < 0;
+  const u64 res = reduce_word(neg ? 0 - c : c, m);
+  return (neg && res != 0) ? m.q - res : res;
+}
+
+// row r of an encoded plaintext -> context limb: the Q-limbs 0 .. level-1, then the P-limbs
+__device__ __forceinline__ u32 enc_limb(u32 r, u32 level, u32 L) {
+  return r < level ? r : L + (r - level);
+}
+
 // Exact a * b mod q for a, b < q and any q < 2^64 (generic entry points only; the context
 // kernels use Shoup/Barrett).  q < 2^63: Barrett / reduce128_wide; above, a 64-step
 // double-and-add.

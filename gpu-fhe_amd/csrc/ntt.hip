@@ -836,7 +836,7 @@ struct Geo {
 // R0: the forward's input range (units of q) its lazy schedule starts from.  The row pass that
 // follows must assume the same R0: fwd_range is not monotonic in it (an earlier reduction can leave
 // a smaller bound), so the key-switch / rescale row kernels, which assume 2 (k_modup_col's
-// outputs), get column passes scheduled from 2 as well (col_fwd_pass, k_rescale_col).
+// outputs), get column passes scheduled from 2 as well (col_fwd_pass, k_lift_col).
 // One column tile (poly p, limb l, tile) of a column pass (the body of k_ntt_col; lds: G::LDS_CF
 // words).
 template <int LOGN, bool FWD, int H, bool NTL, bool NTS, int FI, int R0>
@@ -2016,7 +2016,6 @@ int ntt_dispatch(const fhe_ctx* c, bool fwd, const u64* src, u64 spstride, u64* 
             <<<item_grid(ic), G::THR_C, 0, s>>>(dst, nullptr, dst, nlimbs, limb0, pd, (u32)ic,
                                                 c->d_tw_inv, nf, c->d_mods);
         prof_mark(s, "ntt_col_inv");
-        FHE_HIP_CHECK(hipGetLastError());
         return kOk;
       }
     } else if (split) {
@@ -2028,7 +2027,6 @@ int ntt_dispatch(const fhe_ctx* c, bool fwd, const u64* src, u64 spstride, u64* 
           <<<item_grid(ic), G::THR_C, 0, s>>>(dst, nullptr, dst, nlimbs, limb0, pd, (u32)ic,
                                               c->d_tw_inv, nf, c->d_mods);
       prof_mark(s, "ntt_col_inv");
-      FHE_HIP_CHECK(hipGetLastError());
       return kOk;
     }
     k_ntt_col<LOGN, false, inv_h(HD)>
@@ -2037,7 +2035,6 @@ int ntt_dispatch(const fhe_ctx* c, bool fwd, const u64* src, u64 spstride, u64* 
                              c->d_mods);
     prof_mark(s, "ntt_col_inv");
   }
-  FHE_HIP_CHECK(hipGetLastError());
   return kOk;
 }
 
@@ -2086,141 +2083,68 @@ int hommult_dispatch(const fhe_ctx* c, u64* d, const u64* a, const u64* b, u32 b
          G::THR_C, 0, s>>>(d, nullptr, d, nlimbs, limb0, flat_map(limbN), (u32)ii, c->d_tw_inv,
                            c->d_nfold + 2, c->d_mods);
   prof_mark(s, "hm_col_inv");
-  FHE_HIP_CHECK(hipGetLastError());
   return kOk;
 }
-// Rescale (NTT form): the spread of the last limb over the other limbs folded into the
-// column-forward pass.  last [polys][N] holds INTT(x_last); the tile of limb l (l < nq, the last
-// limb is nq) loads last's columns and spreads them in registers,
-//   v = ((last + h) mod q_last - h) mod q_l,  h = q_last / 2   (galois.hip k_rescale_spread, the
-// path of wide contexts)
-// before the column-forward stages, writing dst [polys][nq][N]: no spread pass and no re-read of
-// its output.  The row pass is k_moddown_row with the q_last^-1 table (the finish).
-template <int LOGN, int H>
-__global__ __launch_bounds__(kColThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void
-k_rescale_col(const u64* __restrict__ last, u64* __restrict__ dst, u32 nq, u32 items,
-              const u64* __restrict__ half, const ulonglong2* __restrict__ tw_all,
-              const ModParams* __restrict__ mods) {
-  using G = Geo<LOGN>;
-  constexpr u64 N = 1ull << LOGN;
-  __shared__ u64 lds[G::LDS_CF];
-  const u32 sub = threadIdx.x % G::SUBS_C, t = threadIdx.x / G::SUBS_C;
-  const LViewC<G::SUBS_C> lv{lds + sub};
-  const u32 it = blockIdx.x;
-  if (it >= items) return;
-  // placement: with 8 | polys, XCD x takes the polys p = x mod 8 and runs the nq limbs of one
-  // (p, tile) back to back, so last's column tile comes from HBM once and from the XCD's L2 for
-  // the other limbs; otherwise limbs fastest over all XCDs
-  const u32 polys = items / (nq * G::TILES_C);
-  u32 tile, l, p;
-  if (polys % 8 == 0) {
-    const u32 k = it / 8;
-    l = k % nq;
-    tile = (k / nq) % G::TILES_C;
-    p = (k / (nq * G::TILES_C)) * 8 + it % 8;
-  } else {
-    l = it % nq;
-    tile = (it / nq) % G::TILES_C;
-    p = it / (nq * G::TILES_C);
+
+// A lift rides on the column-forward pass: src [polys][N] holds one word per coefficient; the tile
+// of row r loads src's columns, lifts them in registers into the limb of row r (the word-level
+// arithmetic is modarith.hpp's lift_centred / lift_signed, shared with the unfused spread kernels
+// that wide contexts take) and runs the column-forward stages, writing one row of dst: no spread
+// pass and no re-read of its output.  The row pass is the caller's.  What differs between the
+// operations is a policy struct passed by value, holding only what the operation needs: rows()
+// of work per poly; limb(r), the context limb of row r; dst_row(r) of dst [polys][dst_rows()][N],
+// where row r is written; prepare(), once per workgroup, yielding the lift of one loaded word.
+
+// Rescale (NTT form): src holds INTT(x_last) of the last limb nq, spread over the limbs l < nq of
+// dst [polys][nq][N]; half[l] = (q_last / 2) mod q_l.  The row pass is k_moddown_row with the
+// q_last^-1 table (the finish).
+struct RescaleLift {
+  u32 nq;
+  const u64* half;
+  __host__ __device__ u32 rows() const { return nq; }
+  __device__ u32 limb(u32 r) const { return r; }
+  __device__ u32 dst_row(u32 r) const { return r; }
+  __device__ u32 dst_rows() const { return nq; }
+  __device__ auto prepare(const ModParams* mods, const ModParams& mi, u32 l) const {
+    const u64 q_last = mods[nq].q, mh = mi.q - half[l];
+    return [=](u64 x, const ModParams& m) { return lift_centred(x, q_last, mh, m); };
   }
-  l = __builtin_amdgcn_readfirstlane(l);
-  const u32 pl = p * nq + l;
-  const u64 col = (u64)tile * G::SUBS_C;
-  u64 x[kE];
-  pass_load<G::N1, true>(GView<G::R2>{const_cast<u64*>(last) + (u64)p * N + col, sub}, t, x);
-  const ModParams ml = mods[nq], mi = mods[l];
-  const u64 h = ml.q >> 1, mh = mi.q - half[l];
-#pragma unroll
-  for (int j = 0; j < kE; ++j) x[j] = csub(reduce_word(csub(x[j] + h, ml.q), mi) + mh, mi.q);
-  // scheduled from 2 (inputs are below q): the range k_moddown_row assumes
-  pass_run<G::N1, true, kNotFinal, kBlockSync, false, H, 2, false, false, G::HALF_C>(
-      x, GView<G::R2>{dst + (u64)pl * N + col, sub}, lv, t, tw_all + (u64)l * N, 1u, mi.q,
-      {0, 0}, {0, 0});
-}
+};
 
-template <int LOGN, int HD>
-int rescale_col_dispatch(const fhe_ctx* c, const u64* last, u64* dst, u32 polys, u32 nq,
-                         const u64* half, hipStream_t s) {
-  using G = Geo<LOGN>;
-  const u64 ic = (u64)polys * nq * G::TILES_C;
-  if (int rc = check_grid(item_blocks(ic), G::THR_C, 1, 1, "rescale_col")) return rc;
-  k_rescale_col<LOGN, HD><<<item_grid(ic), G::THR_C, 0, s>>>(last, dst, nq, (u32)ic, half,
-                                                            c->d_tw_fwd, c->d_mods);
-  return kOk;
-}
-
-// ModRaise: the centred lift of limb 0 into the limbs above it folded into their column-forward
-// pass, as k_rescale_col folds the rescale's spread.  x0 [polys][N] holds INTT_0(limb 0), below
-// q_0; the tile of limb l (1 <= l < nl) loads x0's columns and lifts them in registers,
-//   v = ((x0 + h) mod q_0 - h) mod q_l,  h = q_0 / 2   (galois.hip k_modraise_spread, the path of
-// wide contexts)
-// before the column-forward stages, writing limb l of dst [polys][nl][N]; limb 0 is left to the
-// caller (a copy of the input's).  q_l may be far below q_0 (a 60-bit q_0 over 50-bit primes), so
-// both the lifted word and h go through reduce_word: h mod q_l is two Shoup products per workgroup.
-template <int LOGN, int H>
-__global__ __launch_bounds__(kColThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void
-k_modraise_col(const u64* __restrict__ x0, u64* __restrict__ dst, u32 nl, u32 items,
-               const ulonglong2* __restrict__ tw_all, const ModParams* __restrict__ mods) {
-  using G = Geo<LOGN>;
-  constexpr u64 N = 1ull << LOGN;
-  __shared__ u64 lds[G::LDS_CF];
-  const u32 sub = threadIdx.x % G::SUBS_C, t = threadIdx.x / G::SUBS_C;
-  const LViewC<G::SUBS_C> lv{lds + sub};
-  const u32 it = blockIdx.x;
-  if (it >= items) return;
-  // placement as k_rescale_col: with 8 | polys, XCD x takes the polys p = x mod 8 and runs the
-  // nl - 1 limbs of one (p, tile) back to back (x0's column tile from HBM once, then from the
-  // XCD's L2); otherwise limbs fastest over all XCDs
-  const u32 nq = nl - 1;
-  const u32 polys = items / (nq * G::TILES_C);
-  u32 tile, l, p;
-  if (polys % 8 == 0) {
-    const u32 k = it / 8;
-    l = k % nq;
-    tile = (k / nq) % G::TILES_C;
-    p = (k / (nq * G::TILES_C)) * 8 + it % 8;
-  } else {
-    l = it % nq;
-    tile = (it / nq) % G::TILES_C;
-    p = it / (nq * G::TILES_C);
+// ModRaise: src holds INTT_0(limb 0), below q_0, lifted into the limbs 1 <= l < nl of
+// dst [polys][nl][N]; limb 0 is left to the caller (a copy of the input's).  q_l may be far below
+// q_0 (a 60-bit q_0 over 50-bit primes), so h = q_0 / 2 goes through reduce_word too: two Shoup
+// products per workgroup.
+struct ModRaiseLift {
+  u32 nl;
+  __host__ __device__ u32 rows() const { return nl - 1; }
+  __device__ u32 limb(u32 r) const { return r + 1; }
+  __device__ u32 dst_row(u32 r) const { return r + 1; }
+  __device__ u32 dst_rows() const { return nl; }
+  __device__ auto prepare(const ModParams* mods, const ModParams& mi, u32) const {
+    const u64 q0 = mods[0].q, mh = mi.q - reduce_word(q0 >> 1, mi);
+    return [=](u64 x, const ModParams& m) { return lift_centred(x, q0, mh, m); };
   }
-  l = __builtin_amdgcn_readfirstlane(l + 1);
-  const u64 col = (u64)tile * G::SUBS_C;
-  u64 x[kE];
-  pass_load<G::N1, true>(GView<G::R2>{const_cast<u64*>(x0) + (u64)p * N + col, sub}, t, x);
-  const ModParams m0 = mods[0], mi = mods[l];
-  const u64 h = m0.q >> 1, mh = mi.q - reduce_word(h, mi);
-#pragma unroll
-  for (int j = 0; j < kE; ++j) x[j] = csub(reduce_word(csub(x[j] + h, m0.q), mi) + mh, mi.q);
-  // scheduled from 2 (inputs are below q): the range launch_ntt_row_fwd_r2's row pass assumes
-  pass_run<G::N1, true, kNotFinal, kBlockSync, false, H, 2, false, false, G::HALF_C>(
-      x, GView<G::R2>{dst + ((u64)p * nl + l) * N + col, sub}, lv, t, tw_all + (u64)l * N, 1u, mi.q,
-      {0, 0}, {0, 0});
-}
+};
 
-template <int LOGN, int HD>
-int modraise_col_dispatch(const fhe_ctx* c, const u64* x0, u64* dst, u32 polys, u32 nl,
-                          hipStream_t s) {
-  using G = Geo<LOGN>;
-  const u64 ic = (u64)polys * (nl - 1) * G::TILES_C;
-  if (int rc = check_grid(item_blocks(ic), G::THR_C, 1, 1, "modraise_col")) return rc;
-  k_modraise_col<LOGN, HD><<<item_grid(ic), G::THR_C, 0, s>>>(x0, dst, nl, (u32)ic, c->d_tw_fwd,
-                                                             c->d_mods);
-  return kOk;
-}
+// Encode: src holds signed 64-bit coefficients c (|c| < 2^62 by the call's precondition; any word
+// gives a canonical residue), lifted into every row of dst [polys][nrows][N]: the Q-limbs
+// 0 .. level-1, then the P-limbs (enc_limb).
+struct EncodeLift {
+  u32 nrows, level, L;
+  __host__ __device__ u32 rows() const { return nrows; }
+  __device__ u32 limb(u32 r) const { return enc_limb(r, level, L); }
+  __device__ u32 dst_row(u32 r) const { return r; }
+  __device__ u32 dst_rows() const { return nrows; }
+  __device__ auto prepare(const ModParams*, const ModParams&, u32) const {
+    return [](u64 x, const ModParams& m) { return lift_signed(x, m); };
+  }
+};
 
-// Encode: the lift of the rounded coefficients into every row's residues folded into that row's
-// column-forward pass, as k_modraise_col folds ModRaise's.  cf [polys][N] holds signed 64-bit
-// coefficients c (|c| < 2^62 by the call's precondition; any word gives a canonical residue);
-// the tile of row r loads cf's columns and lifts them in registers,
-//   v = c mod q_limb(r)   (|c| through reduce_word, negated for c < 0, q itself folded to 0;
-//                          encode.hip k_encode_spread is the path of wide contexts)
-// before the column-forward stages, writing row r of dst [polys][rows][N].  Row r is limb
-// r < level ? r : L + r - level: the Q-limbs 0 .. level-1, then the P-limbs.
-template <int LOGN, int H>
+template <int LOGN, int H, class Lift>
 __global__ __launch_bounds__(kColThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void
-k_encode_col(const u64* __restrict__ cf, u64* __restrict__ dst, u32 rows, u32 level, u32 L,
-             u32 items, const ulonglong2* __restrict__ tw_all, const ModParams* __restrict__ mods) {
+k_lift_col(const u64* __restrict__ src, u64* __restrict__ dst, Lift lift, u32 items,
+           const ulonglong2* __restrict__ tw_all, const ModParams* __restrict__ mods) {
   using G = Geo<LOGN>;
   constexpr u64 N = 1ull << LOGN;
   __shared__ u64 lds[G::LDS_CF];
@@ -2228,9 +2152,10 @@ k_encode_col(const u64* __restrict__ cf, u64* __restrict__ dst, u32 rows, u32 le
   const LViewC<G::SUBS_C> lv{lds + sub};
   const u32 it = blockIdx.x;
   if (it >= items) return;
-  // placement as k_rescale_col: with 8 | polys, XCD x takes the polys p = x mod 8 and runs the
-  // rows of one (p, tile) back to back (cf's column tile from HBM once, then from the XCD's L2);
-  // otherwise rows fastest over all XCDs
+  // placement: with 8 | polys, XCD x takes the polys p = x mod 8 and runs the rows of one
+  // (p, tile) back to back, so src's column tile comes from HBM once and from the XCD's L2 for
+  // the other rows; otherwise rows fastest over all XCDs
+  const u32 rows = lift.rows();
   const u32 polys = items / (rows * G::TILES_C);
   u32 tile, r, p;
   if (polys % 8 == 0) {
@@ -2243,32 +2168,30 @@ k_encode_col(const u64* __restrict__ cf, u64* __restrict__ dst, u32 rows, u32 le
     tile = (it / rows) % G::TILES_C;
     p = it / (rows * G::TILES_C);
   }
-  r = __builtin_amdgcn_readfirstlane(r);
-  const u32 l = r < level ? r : L + (r - level);
+  r = __builtin_amdgcn_readfirstlane(r);  // the limb index and all it addresses stay scalar
+  const u32 l = lift.limb(r);
   const u64 col = (u64)tile * G::SUBS_C;
   u64 x[kE];
-  pass_load<G::N1, true>(GView<G::R2>{const_cast<u64*>(cf) + (u64)p * N + col, sub}, t, x);
+  pass_load<G::N1, true>(GView<G::R2>{const_cast<u64*>(src) + (u64)p * N + col, sub}, t, x);
   const ModParams mi = mods[l];
+  const auto f = lift.prepare(mods, mi, l);
 #pragma unroll
-  for (int j = 0; j < kE; ++j) {
-    const bool neg = (int64_t)x[j] < 0;
-    const u64 res = reduce_word(neg ? 0 - x[j] : x[j], mi);
-    x[j] = (neg && res != 0) ? mi.q - res : res;
-  }
-  // scheduled from 2 (inputs are below q): the range launch_ntt_row_fwd_r2's row pass assumes
+  for (int j = 0; j < kE; ++j) x[j] = f(x[j], mi);
+  // scheduled from 2 (inputs are below q): the range the row passes that follow assume
+  // (k_moddown_row, launch_ntt_row_fwd_r2)
   pass_run<G::N1, true, kNotFinal, kBlockSync, false, H, 2, false, false, G::HALF_C>(
-      x, GView<G::R2>{dst + ((u64)p * rows + r) * N + col, sub}, lv, t, tw_all + (u64)l * N, 1u,
-      mi.q, {0, 0}, {0, 0});
+      x, GView<G::R2>{dst + ((u64)p * lift.dst_rows() + lift.dst_row(r)) * N + col, sub}, lv, t,
+      tw_all + (u64)l * N, 1u, mi.q, {0, 0}, {0, 0});
 }
 
-template <int LOGN, int HD>
-int encode_col_dispatch(const fhe_ctx* c, const u64* cf, u64* dst, u32 polys, u32 level, u32 rows,
-                        hipStream_t s) {
+template <int LOGN, int HD, class Lift>
+int lift_col_dispatch(const fhe_ctx* c, const u64* src, u64* dst, u32 polys, const Lift& lift,
+                      const char* who, hipStream_t s) {
   using G = Geo<LOGN>;
-  const u64 ic = (u64)polys * rows * G::TILES_C;
-  if (int rc = check_grid(item_blocks(ic), G::THR_C, 1, 1, "encode_col")) return rc;
-  k_encode_col<LOGN, HD><<<item_grid(ic), G::THR_C, 0, s>>>(cf, dst, rows, level, c->L, (u32)ic,
-                                                           c->d_tw_fwd, c->d_mods);
+  const u64 ic = (u64)polys * lift.rows() * G::TILES_C;
+  if (int rc = check_grid(item_blocks(ic), G::THR_C, 1, 1, who)) return rc;
+  k_lift_col<LOGN, HD><<<item_grid(ic), G::THR_C, 0, s>>>(src, dst, lift, (u32)ic, c->d_tw_fwd,
+                                                         c->d_mods);
   return kOk;
 }
 #endif  // !FHE_NTT_KS_ONLY
@@ -2276,6 +2199,40 @@ int encode_col_dispatch(const fhe_ctx* c, const u64* cf, u64* dst, u32 polys, u3
 }  // namespace
 
 #define FHE_LOGN_CASES(X) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17)
+
+namespace {
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// The one geometry dispatch: (c->log_n, c->wide / c->lz16) -> compile-time (LOGN, HD), handed to
+// f as two integral constants (f(n, hd) names them as template arguments: dispatch<n, hd>(...)),
+// then the launcher's one check for a failed launch.  WIDE_OK = false never instantiates HD = 2
+// (the key-switch kernels; their launchers refuse wide contexts before they get here).
+template <bool WIDE_OK, class F>
+int with_geometry(const fhe_ctx* c, F&& f) {
+  int rc;
+  switch (c->log_n) {
+#define X(n)                                                             \
+  case n:                                                                \
+    if constexpr (WIDE_OK) {                                             \
+      if (c->wide) {                                                     \
+        rc = f(Int<n>{}, Int<2>{});                                      \
+        break;                                                           \
+      }                                                                  \
+    }                                                                    \
+    rc = c->lz16 ? f(Int<n>{}, Int<16>{}) : f(Int<n>{}, Int<8>{});       \
+    break;
+    FHE_LOGN_CASES(X)
+#undef X
+    default:
+      set_error("unsupported log_n");
+      return kUnsupported;
+  }
+  if (rc) return rc;
+  FHE_HIP_CHECK(hipGetLastError());
+  return kOk;
+}
+}  // namespace
 
 #if FHE_NTT_KS_ONLY
 
@@ -2331,7 +2288,18 @@ int ks_row_inner_dispatch(const fhe_ctx* c, const KsRowArgs& a, hipStream_t s) {
       set_error("ks_row_inner: dnum > 4");
       return kUnsupported;
   }
-  FHE_HIP_CHECK(hipGetLastError());
+  return kOk;
+}
+
+template <int LOGN, int HD>
+int row_fwd_r2_pass(const fhe_ctx* c, const u64* src, u64 sp, u64* dst, u64 dp, u32 polys,
+                    u32 limb0, u32 nlimbs, hipStream_t s) {
+  using G = Geo<LOGN>;
+  const u64 ir = (u64)polys * nlimbs * G::TILES_R;
+  if (int rc = check_grid(item_blocks(ir), G::THR_R, 1, 1, "ntt_row_fwd")) return rc;
+  const PolyMap pm{1, sp, 0, dp, 0, 0};
+  k_ntt_row<LOGN, true, HD, false, false, 2><<<item_grid(ir), G::THR_R, 0, s>>>(
+      src, dst, nlimbs, limb0, pm, (u32)ir, c->d_tw_fwd, c->d_mods);
   return kOk;
 }
 }  // namespace
@@ -2340,21 +2308,9 @@ int launch_ntt_col_fwd(const fhe_ctx* c, const u64* src, u64 spstride, u64* dst,
                        u32 polys, u32 limb0, u32 nlimbs, hipStream_t s) {
   if ((u64)polys * nlimbs == 0) return kOk;
   if (c->wide) return wide_unsupported();
-  switch (c->log_n) {
-#define X(n)                                                                                 \
-  case n:                                                                                    \
-    if (int rc = c->lz16 ? col_fwd_pass<n, 16>(c, src, spstride, dst, dpstride, polys, limb0, \
-                                                nlimbs, s)                                   \
-                         : col_fwd_pass<n, 8>(c, src, spstride, dst, dpstride, polys, limb0,  \
-                                              nlimbs, s))                                    \
-      return rc;                                                                             \
-    FHE_HIP_CHECK(hipGetLastError());                                                       \
-    return kOk;
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return with_geometry<false>(c, [&](auto n, auto hd) {
+    return col_fwd_pass<n, hd>(c, src, spstride, dst, dpstride, polys, limb0, nlimbs, s);
+  });
 }
 
 // The row-forward pass over rows that k_modup_col column-passed (its schedule starts from 2):
@@ -2364,27 +2320,9 @@ int launch_ntt_row_fwd_r2(const fhe_ctx* c, const u64* src, u64 spstride, u64* d
                           u32 polys, u32 limb0, u32 nlimbs, hipStream_t s) {
   if ((u64)polys * nlimbs == 0) return kOk;
   if (c->wide) return wide_unsupported();
-  switch (c->log_n) {
-#define X(n)                                                                                      \
-  case n: {                                                                                       \
-    using G = Geo<n>;                                                                             \
-    const u64 ir = (u64)polys * nlimbs * G::TILES_R;                                              \
-    if (int rc = check_grid(item_blocks(ir), G::THR_R, 1, 1, "ntt_row_fwd")) return rc;           \
-    const PolyMap pm{1, spstride, 0, dpstride, 0, 0};                                             \
-    if (c->lz16)                                                                                  \
-      k_ntt_row<n, true, 16, false, false, 2><<<item_grid(ir), G::THR_R, 0, s>>>(                 \
-          src, dst, nlimbs, limb0, pm, (u32)ir, c->d_tw_fwd, c->d_mods);                          \
-    else                                                                                          \
-      k_ntt_row<n, true, 8, false, false, 2><<<item_grid(ir), G::THR_R, 0, s>>>(                  \
-          src, dst, nlimbs, limb0, pm, (u32)ir, c->d_tw_fwd, c->d_mods);                          \
-    FHE_HIP_CHECK(hipGetLastError());                                                             \
-    return kOk;                                                                                   \
-  }
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return with_geometry<false>(c, [&](auto n, auto hd) {
+    return row_fwd_r2_pass<n, hd>(c, src, spstride, dst, dpstride, polys, limb0, nlimbs, s);
+  });
 }
 
 namespace {
@@ -2422,22 +2360,12 @@ int modup_col_dispatch(const fhe_ctx* c, const ModUpColArgs* a, u32 n, hipStream
       set_error("modup_col: digits of more than 4 limbs take the unfused path");
       return kUnsupported;
   }
-  FHE_HIP_CHECK(hipGetLastError());
   return kOk;
 }
-}  // namespace
 
-namespace {
 int launch_modup_group(const fhe_ctx* c, const ModUpColArgs* a, u32 n, hipStream_t s) {
-  switch (c->log_n) {
-#define X(n_) \
-  case n_:    \
-    return c->lz16 ? modup_col_dispatch<n_, 16>(c, a, n, s) : modup_col_dispatch<n_, 8>(c, a, n, s);
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return with_geometry<false>(
+      c, [&](auto logn, auto hd) { return modup_col_dispatch<logn, hd>(c, a, n, s); });
 }
 }  // namespace
 
@@ -2483,19 +2411,8 @@ int moddown_row_dispatch(const fhe_ctx* c, const ModDownRowArgs& a, hipStream_t 
 int launch_moddown_row(const fhe_ctx* c, const ModDownRowArgs& a, hipStream_t s) {
   if ((u64)a.batch * a.nq == 0) return kOk;
   if (c->wide) return wide_unsupported();
-  switch (c->log_n) {
-#define X(n)                                                                                   \
-  case n:                                                                                      \
-    if (int rc = c->lz16 ? moddown_row_dispatch<n, 16>(c, a, s)                              \
-                         : moddown_row_dispatch<n, 8>(c, a, s))                               \
-      return rc;                                                                               \
-    FHE_HIP_CHECK(hipGetLastError());                                                         \
-    return kOk;
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return with_geometry<false>(
+      c, [&](auto n, auto hd) { return moddown_row_dispatch<n, hd>(c, a, s); });
 }
 
 namespace {
@@ -2519,7 +2436,6 @@ int ks_row_fin_dispatch(const fhe_ctx* c, const KsFinArgs& a, hipStream_t s) {
       set_error("ks_row_fin: dnum > 4");
       return kUnsupported;
   }
-  FHE_HIP_CHECK(hipGetLastError());
   return kOk;
 }
 }  // namespace
@@ -2530,29 +2446,14 @@ int launch_ks_row_fin(const fhe_ctx* c, const KsFinArgs& a, hipStream_t s) {
     set_error("ks_row_fin: needs an lz16 context (every modulus below 2^60)");
     return kUnsupported;
   }
-  switch (c->log_n) {
-#define X(n) \
-  case n:    \
-    return ks_row_fin_dispatch<n>(c, a, s);
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return with_geometry<false>(c, [&](auto n, auto) { return ks_row_fin_dispatch<n>(c, a, s); });
 }
 
 int launch_ks_row_inner(const fhe_ctx* c, const KsRowArgs& a, hipStream_t s) {
   if ((u64)a.rows * a.batch == 0) return kOk;
   if (c->wide) return wide_unsupported();
-  switch (c->log_n) {
-#define X(n) \
-  case n:    \
-    return c->lz16 ? ks_row_inner_dispatch<n, 16>(c, a, s) : ks_row_inner_dispatch<n, 8>(c, a, s);
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return with_geometry<false>(
+      c, [&](auto n, auto hd) { return ks_row_inner_dispatch<n, hd>(c, a, s); });
 }
 
 #else
@@ -2566,20 +2467,10 @@ int launch_ntt_strided(const fhe_ctx* c, bool forward, const u64* src, u64 spstr
                        u64 dpstride, u32 polys, u32 limb0, u32 nlimbs, hipStream_t s,
                        const ulonglong2* nfold, bool split) {
   if ((u64)polys * nlimbs == 0) return kOk;
-  switch (c->log_n) {
-#define X(n) \
-  case n:    \
-    return c->wide   ? ntt_dispatch<n, 2>(c, forward, src, spstride, dst, dpstride, polys, limb0, \
-                                          nlimbs, s, nfold, split)                              \
-           : c->lz16 ? ntt_dispatch<n, 16>(c, forward, src, spstride, dst, dpstride, polys, limb0, \
-                                           nlimbs, s, nfold, split)                             \
-                     : ntt_dispatch<n, 8>(c, forward, src, spstride, dst, dpstride, polys, limb0,  \
-                                          nlimbs, s, nfold, split);
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return with_geometry<true>(c, [&](auto n, auto hd) {
+    return ntt_dispatch<n, hd>(c, forward, src, spstride, dst, dpstride, polys, limb0, nlimbs, s,
+                               nfold, split);
+  });
 }
 
 namespace {
@@ -2615,26 +2506,10 @@ int launch_ntt_col_inv(const fhe_ctx* c, const u64* src, u64 spstride, u64* dst,
                        u32 polys, u32 limb0, u32 nlimbs, hipStream_t s, const ulonglong2* nfold,
                        bool split) {
   if ((u64)polys * nlimbs == 0) return kOk;
-  int rc = kUnsupported;
-  switch (c->log_n) {
-#define X(n)                                                                                     \
-  case n:                                                                                        \
-    rc = c->wide   ? col_inv_dispatch<n, 2>(c, src, spstride, dst, dpstride, polys, limb0,      \
-                                            nlimbs, s, nfold, split)                            \
-         : c->lz16 ? col_inv_dispatch<n, 16>(c, src, spstride, dst, dpstride, polys, limb0,     \
-                                             nlimbs, s, nfold, split)                           \
-                   : col_inv_dispatch<n, 8>(c, src, spstride, dst, dpstride, polys, limb0,      \
-                                            nlimbs, s, nfold, split);                           \
-    break;
-    FHE_LOGN_CASES(X)
-#undef X
-    default:
-      set_error("unsupported log_n");
-      return kUnsupported;
-  }
-  if (rc) return rc;
-  FHE_HIP_CHECK(hipGetLastError());
-  return kOk;
+  return with_geometry<true>(c, [&](auto n, auto hd) {
+    return col_inv_dispatch<n, hd>(c, src, spstride, dst, dpstride, polys, limb0, nlimbs, s, nfold,
+                                   split);
+  });
 }
 
 size_t hommult_workspace_bytes(const fhe_ctx* c, u32 batch, u32 nlimbs) {
@@ -2643,17 +2518,9 @@ size_t hommult_workspace_bytes(const fhe_ctx* c, u32 batch, u32 nlimbs) {
 
 static int hommult_chunk(const fhe_ctx* c, u64* d, const u64* a, const u64* b, u32 batch,
                          u32 limb0, u32 nlimbs, u64* x, hipStream_t s) {
-  switch (c->log_n) {
-#define X(n) \
-  case n:    \
-    return c->wide   ? hommult_dispatch<n, 2>(c, d, a, b, batch, limb0, nlimbs, x, s)  \
-           : c->lz16 ? hommult_dispatch<n, 16>(c, d, a, b, batch, limb0, nlimbs, x, s) \
-                     : hommult_dispatch<n, 8>(c, d, a, b, batch, limb0, nlimbs, x, s);
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return with_geometry<true>(c, [&](auto n, auto hd) {
+    return hommult_dispatch<n, hd>(c, d, a, b, batch, limb0, nlimbs, x, s);
+  });
 }
 
 // (Measured no gain, DESIGN.md §8: two half-batch pipelines on two streams, 37.2k vs 36.9k
@@ -2665,70 +2532,39 @@ int launch_hommult(const fhe_ctx* c, u64* d, const u64* a, const u64* b, u32 bat
   return hommult_chunk(c, d, a, b, batch, limb0, nlimbs, static_cast<u64*>(ws), s);
 }
 
+namespace {
+// who: the check_grid label; what: the operation, for the refusal of wide contexts (they take
+// the unfused spread kernels, which never call this)
+template <class Lift>
+int launch_lift_col(const fhe_ctx* c, const u64* src, u64* dst, u32 polys, const Lift& lift,
+                    const char* who, const char* what, hipStream_t s) {
+  if (c->wide) {
+    set_error(std::string(who) + ": the fused " + what + " needs every modulus < 2^61");
+    return kUnsupported;
+  }
+  return with_geometry<false>(c, [&](auto n, auto hd) {
+    return lift_col_dispatch<n, hd>(c, src, dst, polys, lift, who, s);
+  });
+}
+}  // namespace
+
 int launch_rescale_col(const fhe_ctx* c, const u64* last, u64* dst, u32 polys, u32 nq,
                        const u64* half, hipStream_t s) {
   if ((u64)polys * nq == 0) return kOk;
-  if (c->wide) {
-    set_error("rescale_col: the fused rescale needs every modulus < 2^61");
-    return kUnsupported;
-  }
-  switch (c->log_n) {
-#define X(n)                                                  \
-  case n:                                                     \
-    if (int rc = c->lz16 ? rescale_col_dispatch<n, 16>(c, last, dst, polys, nq, half, s) \
-                         : rescale_col_dispatch<n, 8>(c, last, dst, polys, nq, half, s))  \
-      return rc;                                              \
-    FHE_HIP_CHECK(hipGetLastError());                         \
-    return kOk;
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return launch_lift_col(c, last, dst, polys, RescaleLift{nq, half}, "rescale_col", "rescale", s);
 }
 
 int launch_modraise_col(const fhe_ctx* c, const u64* x, u64* dst, u32 polys, u32 out_level,
                         hipStream_t s) {
   if (polys == 0 || out_level < 2) return kOk;
-  if (c->wide) {
-    set_error("modraise_col: the fused ModRaise needs every modulus < 2^61");
-    return kUnsupported;
-  }
-  switch (c->log_n) {
-#define X(n)                                                                        \
-  case n:                                                                           \
-    if (int rc = c->lz16 ? modraise_col_dispatch<n, 16>(c, x, dst, polys, out_level, s) \
-                         : modraise_col_dispatch<n, 8>(c, x, dst, polys, out_level, s))  \
-      return rc;                                                                    \
-    FHE_HIP_CHECK(hipGetLastError());                                               \
-    return kOk;
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return launch_lift_col(c, x, dst, polys, ModRaiseLift{out_level}, "modraise_col", "ModRaise", s);
 }
 
 int launch_encode_col(const fhe_ctx* c, const u64* cf, u64* dst, u32 polys, u32 level, u32 rows,
                       hipStream_t s) {
   if (polys == 0 || rows == 0) return kOk;
-  if (c->wide) {
-    set_error("encode_col: the fused encode needs every modulus < 2^61");
-    return kUnsupported;
-  }
-  switch (c->log_n) {
-#define X(n)                                                                             \
-  case n:                                                                                \
-    if (int rc = c->lz16 ? encode_col_dispatch<n, 16>(c, cf, dst, polys, level, rows, s) \
-                         : encode_col_dispatch<n, 8>(c, cf, dst, polys, level, rows, s))  \
-      return rc;                                                                         \
-    FHE_HIP_CHECK(hipGetLastError());                                                    \
-    return kOk;
-    FHE_LOGN_CASES(X)
-#undef X
-  }
-  set_error("unsupported log_n");
-  return kUnsupported;
+  return launch_lift_col(c, cf, dst, polys, EncodeLift{rows, level, c->L}, "encode_col", "encode",
+                         s);
 }
 
 #endif  // FHE_NTT_KS_ONLY

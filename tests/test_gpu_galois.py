@@ -73,16 +73,31 @@ def test_rescale_coeff_matches_oracle(fc, log_n, L, polys):
         assert (got[p].astype(object) == want).all()
 
 
-@pytest.mark.parametrize("log_n,L,polys", [(10, 3, 2), (14, 4, 1), (16, 8, 2)])
-def test_rescale_ntt_matches_oracle(fc, log_n, L, polys):
-    ctx = fc.Context(log_n, L=L)
-    x = rand(ctx.moduli, log_n, (polys,), seed=L + 1)
+def check_rescale_ntt(fc, ctx, log_n, polys, seed):
+    x = rand(ctx.moduli, log_n, (polys,), seed=seed)
     got = fc.to_host(ctx.rescale(fc.to_device(x), ntt_form=True))
     for p in range(polys):
         c = coracle.ntt_inv(x[p][None], ctx.moduli)[0]
         r = pyoracle.rescale_coeff(c.astype(object), ctx.moduli)
         want = coracle.ntt_fwd(np.asarray(r, dtype=np.uint64)[None], ctx.moduli[:-1])[0]
         assert (got[p] == want).all()
+
+
+# polys 8: the fused lift's placement with 8 | polys (rows of one (poly, tile) back to back);
+# polys 9: more than 8 and no multiple of it (rows fastest)
+@pytest.mark.parametrize("log_n,L,polys", [(10, 3, 2), (14, 4, 1), (16, 8, 2), (10, 3, 8),
+                                           (10, 4, 9)])
+def test_rescale_ntt_matches_oracle(fc, log_n, L, polys):
+    check_rescale_ntt(fc, fc.Context(log_n, L=L), log_n, polys, seed=L + 1)
+
+
+def test_rescale_ntt_wide_chain_matches_oracle(fc):
+    """A 62-bit chain: the unfused spread (k_rescale_spread), which shares the word-level lift
+    with the fused kernel."""
+    log_n, L, polys = 10, 3, 2
+    ctx = fc.Context(log_n, moduli=fc.gen_moduli(log_n, L, bits=62))
+    assert min(ctx.moduli) >= 1 << 61
+    check_rescale_ntt(fc, ctx, log_n, polys, seed=L + 1)
 
 
 def test_rescale_partial_level_and_errors(fc):

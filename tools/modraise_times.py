@@ -2,7 +2,7 @@
 dnum = 4, batch 32), from level 1 to levels 16 and 4, in one process, three forms of one result:
 
   * fused:    the shipped path of narrow contexts -- inverse NTT of limb 0, the lift folded into
-              the column-forward pass of the limbs above it (k_modraise_col), row-forward pass,
+              the column-forward pass of the limbs above it (k_lift_col), row-forward pass,
               copy of limb 0;
   * unfused:  the path of wide contexts forced on the same context (FHECORE_MODRAISE_UNFUSED=1,
               read by every call) -- a separate spread pass into the output, then a whole forward
