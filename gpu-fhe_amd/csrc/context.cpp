@@ -97,12 +97,14 @@ int ctx_create(fhe_ctx** out, u32 log_n, const u64* q, u32 L, const u64* p, u32 
   // table: narrow contexts at N = 2^16 (Q limbs only: HomMult never runs on P limbs)
   const bool split9 = log_n == 16 && !c->wide;
   std::vector<Pair64> twf9(split9 ? L * n : 0);
+  std::vector<Pair64> nfold_pair(split9 ? 4 * L : 0);  // [L][4], entries 0, 1 (d_nfold's stride)
   c->psi.resize(M);
   c->mods_host.resize(M);
   for (size_t i = 0; i < M; ++i) {
     c->mods_host[i] = make_mod_params(mods[i]);
     c->psi[i] = ntt_tables(mods[i], log_n, &twf[i * n], &twi[i * n], &nfold[4 * i],
-                           split9 && i < L ? &twf9[i * n] : nullptr);
+                           split9 && i < L ? &twf9[i * n] : nullptr,
+                           split9 && i < L ? &nfold_pair[4 * i] : nullptr);
   }
   // encode / decode (encode.hip): the special FFT's roots and rotation-group powers, and
   // q_0^-1 mod q_1 for decode's two-limb centring
@@ -125,6 +127,8 @@ int ctx_create(fhe_ctx** out, u32 log_n, const u64* q, u32 L, const u64* p, u32 
       (rc = upload(&c->d_nfold, reinterpret_cast<const ulonglong2*>(nfold.data()), 4 * M)) ||
       (split9 && (rc = upload(&c->d_tw_fwd9, reinterpret_cast<const ulonglong2*>(twf9.data()),
                               (size_t)L * n))) ||
+      (split9 && (rc = upload(&c->d_nfold_pair,
+                              reinterpret_cast<const ulonglong2*>(nfold_pair.data()), 4 * L))) ||
       (rc = upload(&c->d_enc_roots, reinterpret_cast<const double2*>(roots.data()), 2 * n)) ||
       (rc = upload(&c->d_enc_rot, rot.data(), n / 2)) ||
       (rc = upload(&c->d_conj_w, reinterpret_cast<const ulonglong2*>(conjw.data()), L)) ||
@@ -141,7 +145,7 @@ int ctx_destroy(fhe_ctx* c) {
   if (!c) return kOk;
   (void)hipSetDevice(c->device);
   for (auto& t : c->bc_tables) (void)hipFree(t.second);
-  for (void* ptr : {(void*)c->d_mods, (void*)c->d_tw_fwd, (void*)c->d_tw_fwd9, (void*)c->d_tw_inv, (void*)c->d_nfold, (void*)c->d_nfold_down, (void*)c->d_nfold_up,
+  for (void* ptr : {(void*)c->d_mods, (void*)c->d_tw_fwd, (void*)c->d_tw_fwd9, (void*)c->d_tw_inv, (void*)c->d_nfold, (void*)c->d_nfold_pair, (void*)c->d_nfold_down, (void*)c->d_nfold_up,
                     (void*)c->d_modup_inv, (void*)c->d_modup_hat, (void*)c->d_moddown_inv,
                     (void*)c->d_moddown_hat, (void*)c->d_modup_hat_w, (void*)c->d_modup_hat_rw,
                     (void*)c->d_moddown_hat_w, (void*)c->d_modup_hat_rwp,

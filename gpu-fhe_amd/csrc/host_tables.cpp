@@ -173,7 +173,8 @@ void lane_major_rows(Pair64* tw, size_t entries, u32 log_n, int elog, int n1, in
     }
 }
 
-u64 ntt_tables(u64 q, u32 log_n, Pair64* twf, Pair64* twi, Pair64* nfold, Pair64* twf9) {
+u64 ntt_tables(u64 q, u32 log_n, Pair64* twf, Pair64* twi, Pair64* nfold, Pair64* twf9,
+               Pair64* nfold2) {
   const u64 n = 1ull << log_n;
   const u64 psi = find_psi(q, log_n), psi_inv = powmod_u64(psi, q - 2, q);
   std::vector<u64> pw(n), pwi(n);
@@ -194,6 +195,11 @@ u64 ntt_tables(u64 q, u32 log_n, Pair64* twf, Pair64* twi, Pair64* nfold, Pair64
   nfold[1] = shoup_pair(nf1, q);
   nfold[2] = shoup_pair(mulmod_u64(n_inv, r_mod, q), q);  // HomMult: undo the tensor's R^-1
   nfold[3] = shoup_pair(mulmod_u64(nf1, r_mod, q), q);
+  if (nfold2) {  // the pair tensor's inverse rows skip the stage that doubles: 2 N^-1 R
+    const u64 r2 = mulmod_u64(2 % q, r_mod, q);
+    nfold2[0] = shoup_pair(mulmod_u64(n_inv, r2, q), q);
+    nfold2[1] = shoup_pair(mulmod_u64(nf1, r2, q), q);
+  }
   if (twf9) {  // the 512 x 128 split's forward rows (HomMult at N = 2^16: k_hm_col9 + 7-stage rows)
     std::copy(twf, twf + n, twf9);
     lane_major_rows(twf9, n, log_n, 4, (int)log_n / 2 + 1, 4);  // rounds 3 + 4 (SMALL_FIRST)

@@ -26,8 +26,10 @@ bool gen_moduli_host(u32 log_n, u32 count, u32 bits, u32 skip, u64* out, std::st
 // row passes' lane-major layout (lane_major_rows), and nfold [4]: N^-1, psi^-1 N^-1 and the same
 // times R = 2^64 (the fused HomMult's Montgomery tensor).  psi is returned.  twf9 (optional): the
 // forward table laid out for rows of the (log_n / 2 + 1) x rest split (the HomMult's 512 x 128
-// forward at N = 2^16).
-u64 ntt_tables(u64 q, u32 log_n, Pair64* twf, Pair64* twi, Pair64* nfold, Pair64* twf9 = nullptr);
+// forward at N = 2^16).  nfold2 (optional) [2]: 2 N^-1 R and 2 psi^-1 N^-1 R, the fold of the
+// HomMult path whose inverse rows skip their first, doubling stage (ntt.hip k_hommult_row PAIR).
+u64 ntt_tables(u64 q, u32 log_n, Pair64* twf, Pair64* twi, Pair64* nfold, Pair64* twf9 = nullptr,
+               Pair64* nfold2 = nullptr);
 // Row-pass twiddle layout: the low-bit round's stage segments of each n-entry table stored
 // transposed (see host_tables.cpp); a permutation within each segment.  n1: column stages of the
 // split (default log_n / 2); kb_last: stages of the low-bit round (default: ntt.hip Rounds').

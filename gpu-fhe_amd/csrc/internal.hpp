@@ -75,6 +75,11 @@ struct fhe_ctx {
   // [L + K][4] Shoup pairs: N^-1, psi^-1 N^-1 (last inverse stage), and the same times
   // R = 2^64 (HomMult's inverse, undoing the Montgomery tensor's R^-1)
   ulonglong2* d_nfold = nullptr;
+  // [L][4], entries 0 and 1: 2 N^-1 R and 2 psi^-1 N^-1 R, the column inverse's fold after the
+  // pair tensor (ntt.hip k_hommult_row PAIR: its inverse rows skip the first stage and its
+  // doubling); allocated with d_tw_fwd9, else null.  Same [limb][4] stride as d_nfold, which every
+  // column inverse indexes.
+  ulonglong2* d_nfold_pair = nullptr;
   // rescale: [L][L] Shoup pairs of q_l^-1 mod q_i and (q_l / 2) mod q_i, row l = last limb
   ulonglong2* d_rs_tab = nullptr;
   uint64_t* d_rs_half = nullptr;

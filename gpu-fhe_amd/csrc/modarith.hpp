@@ -263,6 +263,10 @@ __device__ __forceinline__ void mul2_wide61(u64 A, u64 B, u64 C, u64 D, u64& tlo
 // below q).  The middle column (2D products < 2^61 each) stays below 2^64, the high one far below;
 // the low column's carries are counted straight from the mads' carry-outs (v_addc with the carry
 // SGPR as carry-in).  24 VALU for D = 4 where the compiler's u128 lowering takes 55.
+// Also exact for k_d up to 2^61 (the HomMult pair tensor's 4-term sums, operands at most 2q with
+// q < 2^60): a high half is then below 2^29, the 8 middle products sum to at most
+// 8 (2^32 - 1)(2^29 - 1) < 2^64 - 2^35, and its high word plus the 4 carries stays below 2^32
+// (tests/test_hommult_pairs_model.py).
 template <int D>
 __device__ __forceinline__ void dot_wide61(const u64 (&x)[D], const u64 (&k)[D], u64& tlo,
                                            u64& thi) {

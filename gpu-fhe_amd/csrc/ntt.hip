@@ -20,6 +20,10 @@
 // HomMult (config 3) = 3 launches: column-forward of a and b's 4 polys -> one fused row kernel
 // (row-forward x4, tensor d0 = A0B0, d1 = A0B1 + A1B0, d2 = A1B1 in LDS, row-inverse x3) ->
 // column-inverse on the 3 output polys.  Moduli of 61-63 bits take exact butterflies (H = 2).
+// At N = 2^16 with every modulus below 2^60 (lz16) the shape is 9 + 6 | pairs | 7 + 8: a 9-stage
+// column forward (k_hm_col9), 6-stage forward rows, the tensor on the adjacent pairs in place of the
+// forward's last and the inverse's first stage, 7-stage inverse rows and the 8-stage column inverse
+// folding 2 N^-1 R (hm_row_pairs).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -289,8 +293,12 @@ constexpr int fwd_range(int r0, int stages, int H) {
 // in the stages + 8 at the end (every element above 3q back below 2q for the exchange) instead of
 // 32 conditional subtractions.
 constexpr int gs_red(int r) { return r > 8 ? 2 : r; }
-constexpr int gs_in(int j, int k) {
-  int r = 3;
+// r0: the round's input range.  3 everywhere but the pair tensor's 3-stage first inverse round
+// (k_hommult_row PAIR), whose inputs are REDC outputs below 2q: its sums run 2 -> 4 -> 8 -> 16
+// without a reduction inside the round (the 4-stage schedule from 3 reduces its pairs at 12), and
+// every element that did not leave a Shoup product last (below 3q) is taken below 2q at the end.
+constexpr int gs_in(int j, int k, int r0 = 3) {
+  int r = r0;
   for (int b = 0; b < k; ++b) r = ((j >> b) & 1) ? 3 : 2 * gs_red(r);
   return r;
 }
@@ -306,9 +314,10 @@ constexpr int gs_in(int j, int k) {
 // are stored lane-major.
 // PRE0 (forward, k_modup_col): the operands of stage 0's products arrive already multiplied by
 // its twiddle (the base conversion folds it into its constants), so stage 0 only adds.
+// GIN (inverse, H = 16): the round's input range in units of q (gs_in's r0).
 template <int LOGR, int KB, int LO, bool FWD, int FIN, bool GATHER = false, int H = 8,
           int RIN = 8, bool ROWTAB = GATHER, bool CHAIN = GATHER, bool PRE0 = false,
-          int EL = kElog>
+          int EL = kElog, int GIN = 3>
 __device__ __forceinline__ void round_compute(u64 (&x)[1 << EL], const u32 tp,
                                               const ulonglong2* __restrict__ tw, const u32 base,
                                               const u64 q, const ulonglong2 nf0,
@@ -316,6 +325,11 @@ __device__ __forceinline__ void round_compute(u64 (&x)[1 << EL], const u32 tp,
   using Lay = Layout<LOGR, KB, LO, EL>;
   using TS = TwSlots<LOGR, KB, LO, EL>;
   constexpr int E = Lay::E;
+  // the round sits inside the low EL position bits (the low-bit round, or the pair tensor's
+  // neighbours that leave bit 0 out): thread t owns positions t 2^EL + [0, 2^EL), and the row
+  // tables store these stages lane-major
+  constexpr bool kLane = ROWTAB && LO + KB <= EL;
+  static_assert(!kLane || Lay::jmask == (u32)E - 1, "lane-major stages: elements = the low bits");
   ulonglong2 tws[GATHER && TS::T.ns > 0 ? TS::T.ns : 1];
   if constexpr (GATHER) {
     static_for<0, TS::T.ns>([&](auto sc) {
@@ -328,14 +342,14 @@ __device__ __forceinline__ void round_compute(u64 (&x)[1 << EL], const u32 tp,
         // tp = t << kElog); the row tables store those stages lane-major (host_tables.cpp
         // lane_major_rows), so the load index is sj TPS + t and a wavefront reads contiguous words
         const u32 sj = Lay::jpos(TS::T.rep_j[sl]) >> (bitpos + 1);
-        const u32 g = (ROWTAB && LO == 0) ? sj * ((1u << LOGR) / E) + (tp >> EL)
+        const u32 g = kLane ? sj * ((1u << LOGR) / E) + (tp >> EL)
                                           : (tp >> (bitpos + 1)) | sj;
         tws[sl] = ld_tw(tw + (base << st) + g);
       }
     });
     asm volatile("" ::: "memory");
   }
-  static_assert(GATHER || !(ROWTAB && LO == 0), "lane-major row twiddles are gathered");
+  static_assert(GATHER || !kLane, "lane-major row twiddles are gathered");
   auto twiddle = [&](int b, int j, int bitpos, int st) {
     if constexpr (GATHER) return tws[TS::T.slot[b][j]];
     // (kTpBelow: tp >> (bitpos + 1) is 0, written out so the address is visibly uniform and the
@@ -469,7 +483,7 @@ __device__ __forceinline__ void round_compute(u64 (&x)[1 << EL], const u32 tp,
         constexpr int j = decltype(jc)::value;
         if constexpr (!(j & (1 << b))) {
           constexpr int jj = j | (1 << b);
-          constexpr int r = gs_in(j, b), rr = gs_red(r);
+          constexpr int r = gs_in(j, b, GIN), rr = gs_red(r);
           u64 u = x[j], v = x[jj];
           if constexpr (rr != r) {
             u = top_bits<GATHER>(u, sb, nq);
@@ -499,7 +513,7 @@ __device__ __forceinline__ void round_compute(u64 (&x)[1 << EL], const u32 tp,
     } else {
       static_for<0, E>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        if constexpr (gs_in(j, KB) > 3) x[j] = top_bits<GATHER>(x[j], sb, nq);
+        if constexpr (gs_in(j, KB, GIN) > 3) x[j] = top_bits<GATHER>(x[j], sb, nq);
       });
     }
   } else {
@@ -1036,6 +1050,179 @@ struct HmGeo {
 constexpr bool kHmNT = true;
 constexpr bool kKsNT = true;
 
+// The fused row kernel on pairs (k_hommult_row<16, 16, true>: N = 2^16, lz16 contexts, after
+// k_hm_col9).  The last forward stage and the first inverse stage butterfly the same adjacent
+// pair (2i, 2i + 1) of a row on either side of the pointwise tensor, and that pair lives in one
+// thread in both layouts, so neither stage is run: with a = (a0, a1), b = (b0, b1) the pair before
+// the last forward stage and z its twiddle,
+//   (a0 + z a1)(b0 + z b1) + (a0 - z a1)(b0 - z b1)          = 2 (a0 b0 + z^2 a1 b1)
+//   ((a0 + z a1)(b0 + z b1) - (a0 - z a1)(b0 - z b1)) z^-1   = 2 (a0 b1 + a1 b0)
+// i.e. twice the product of two degree-1 polynomials mod X^2 - z^2.  The factor 2 goes into the
+// column inverse's fold (d_nfold_pair: 2 N^-1 R).
+//   forward rows: 6 stages in rounds of 3 + 3 (position bits 6-4, then 3-1; bit 0 is the spare
+//     element bit of both rounds, so round 0 still loads 16-byte pairs and round 1 holds the 16
+//     words t 16 + [0, 16) with lane-major twiddles), outputs below 8q taken below 2q (top_bits);
+//     the B groups also store b1' = z^2 b1, one exact-quotient Shoup product per pair.  z^2 needs
+//     no table: in the psi^brv order tw[2k]^2 = tw[k] and tw[2k + 1]^2 = -tw[k], so z^2 is +/- the
+//     previous stage's twiddle of the same pair (sign: bit 1 of the position, a compile-time
+//     property of the element index), re-read here: the words round 1 just gathered, so cache
+//     hits, instead of threading round_compute's register copies out of it;
+//   tensor: d0 = (a0 b0 + a1 b1', a0 b1 + a1 b0) of (A0, B0), d2 the same of (A1, B1), d1 the
+//     4-term sums over (A0, B1) and (A1, B0); each output one 128-bit sum and one REDC.  Bounds:
+//     a0, a1, b0, b1 < 2q and b1' <= 2q (shoup_fast's [0, 2q), or 2q minus it), all < 2^61 because
+//     lz16 guarantees q < 2^60 (asserted at dispatch); a 4-term sum is below 16 q^2 < q 2^64, the
+//     precondition of mont_redc_x; the partial-product columns: mul2_wide61, dot_wide61;
+//   inverse rows: 7 stages, 3 (bits 1-3, inputs the REDC outputs below 2q: gs_in from 2, no
+//     reduction inside the round) + 4 (bits 4-7, unchanged).
+// LDS per row: the four padded slots of the full form (272 words: one pad word per 16) and 192
+// more words, 1280 in all: 40 KiB per workgroup, so four workgroups per CU remain.  The 2 x 128
+// b1' values fill the 192 extra words and the 64 pad words, which no slot access touches (position p
+// sits at p + p / 16, never at 17 h + 16): thread t's pair k of B poly s goes to extra word
+// (6 s + k) 16 + t for k < 6 (lanes on consecutive words) and for k = 6, 7 to pad word t of slot
+// 2 s + k - 6.  Every LDS address of a thread is then 17 t or t plus a compile-time offset.  (The four
+// slots without pad words behind an XOR swizzle also fit 40 KiB, but every access then computes its
+// own address and none pair up: +2.6 % VALU and twice the LDS instructions of the full form,
+// profiles/r07_pairs_pmc.txt.)
+constexpr int kPairRoww = 4 * 272 + 192;
+// word of b1' (B poly s, pair k, thread t) in a row's LDS
+__device__ __forceinline__ u32 pair_bp_idx(int s, int k, u32 t) {
+  return k < 6 ? 4 * 272 + (6 * s + k) * 16 + t : (2 * s + k - 6) * 272 + 17 * t + 16;
+}
+template <int LOGN>
+__device__ __forceinline__ void hm_row_pairs(u64* lds, const u64* __restrict__ x,
+                                             u64* __restrict__ d, u32 nlimbs, u32 limb0,
+                                             const ulonglong2* __restrict__ twf,
+                                             const ulonglong2* __restrict__ twi,
+                                             const ModParams* __restrict__ mods) {
+  using G = Geo<LOGN>;
+  using H = HmGeo<LOGN>;
+  static_assert(LOGN == 16 && G::N2 == 8 && H::TPS == 16 && kElog == 4 && G::R2 == 256,
+                "built for N = 2^16: 256-word rows, 16 threads per row");
+  constexpr u64 N = 1ull << LOGN;
+  constexpr int HR = 16;
+  constexpr int SY = H::SYNC_ROUND, ST = H::SYNC_TENSOR;
+  u32 l, rest;
+  xcd_limb_split(blockIdx.x, nlimbs, gridDim.x / nlimbs, l, rest);
+  const u32 b = rest / H::TILES, tile = rest % H::TILES;
+  const u32 limb = limb0 + l;
+  const ModParams m = mods[limb];
+  const u64 q = m.q, nq = 0 - q;
+  const u64 limbN = (u64)nlimbs * N;
+  // poly-major groups are whole wavefronts (HmGeo): the group is wave-uniform
+  const u32 grp =
+      __builtin_amdgcn_readfirstlane((threadIdx.x / (H::ROWS * H::TPS) + blockIdx.x) % 4);
+  const u32 sub = (threadIdx.x / H::TPS) % H::ROWS;
+  const u32 t = threadIdx.x % H::TPS;
+  const u32 row = tile * H::ROWS + sub;
+  const u64 loc = (u64)l * N + (u64)row * G::R2;
+  const ulonglong2* tf9 = twf + (u64)limb * N;
+  const ulonglong2* ti = twi + (u64)limb * N;
+  const u32 base = (u32)G::R1 + row;
+  static_assert(G::RS == 272, "four padded slots and 192 extra words per row");
+  u64* rowlds = lds + sub * kPairRoww;
+  const LView<1, true> own{rowlds + grp * G::RS};
+  u64 v[kE];
+
+  // forward rows: the 512 x 128 split's rows, two per 256-word row, 6 of their 7 stages
+  using F0 = Layout<7, 3, 4>;
+  using F1 = Layout<7, 3, 1>;
+  static_assert(F0::jpos(kE / 2) == 1 && F1::jpos(kE / 2) == 1, "the spare element bit is bit 0");
+  const u32 h7 = t >> 3, t7 = t & 7;
+  const u32 base7 = 2u * (u32)G::R1 + 2 * row + h7;
+  const u32 tp0 = F0::tpos(t7), tp1 = F1::tpos(t7);
+  constexpr int RIN0 = fwd_range(1, G::N1 + 1, HR), RIN1 = fwd_range(RIN0, 3, HR);
+  static_assert(fwd_range(RIN1, 3, HR) > 4 && fwd_range(RIN1, 3, HR) <= 16,
+                "the 6-stage outputs are within top_bits' reach");
+  {
+    const gptr_u128 gin = (gptr_u128)(const_cast<u64*>(x) + ((u64)b * 4 + grp) * limbN + loc +
+                                      h7 * 128 + tp0);
+#pragma unroll
+    for (int j = 0; j < kE / 2; ++j) {
+      const u64x2_t w2 = gld<kHmNT>(gin + F0::jpos(j) / 2);
+      v[j] = w2.x;
+      v[j + kE / 2] = w2.y;
+    }
+  }
+  round_compute<7, 3, 4, true, kNotFinal, true, HR, RIN0>(v, tp0, tf9, base7, q, {0, 0}, {0, 0});
+  own.template store<F0>(v, h7 * 128 + tp0);
+  lds_sync<SY>();
+  own.template load<F1>(v, h7 * 128 + tp1);
+  round_compute<7, 3, 1, true, kFinalFwd2, true, HR, RIN1>(v, tp1, tf9, base7, q, {0, 0}, {0, 0});
+  lds_sync<SY>();
+  own.template store<F1>(v, h7 * 128 + tp1);
+  if (grp >= 2) {
+    // b1' = z^2 b1: pair k = (v[k], v[k + 8]) at positions tp1 + 2k (+ 1); its last-stage twiddle
+    // is entry (base7 << 6) + 8 t7 + k, whose square is +/- entry (base7 << 5) + 4 t7 + (k >> 1),
+    // stored lane-major at (k >> 1) 8 + t7, minus for odd k
+    const int sB = grp - 2;
+    const ulonglong2* tz = tf9 + ((u64)base7 << 5) + t7;
+    u64 q2 = 2 * q;
+    asm("" : "+s"(q2));
+#pragma unroll
+    for (int k = 0; k < kE / 2; ++k) {
+      const ulonglong2 w = ld_tw(tz + (k >> 1) * 8);
+      const u64 r = shoup_fast(v[k + kE / 2], w.x, w.y, nq);  // [0, 2q)
+      const u64 bv = (k & 1) ? q2 - r : r;  // (0, 2q] for the odd pairs
+      rowlds[sB ? pair_bp_idx(1, k, t) : pair_bp_idx(0, k, t)] = bv;
+    }
+  }
+  lds_sync<ST>();
+
+  // tensor on pairs, outputs in the first inverse round's layout (v[k], v[k + 8]) = pair k
+  using I0 = Layout<G::N2, 3, 1>;
+  using I1 = Layout<G::N2, 4, 4>;
+  static_assert(I0::jpos(kE / 2) == 1 && I0::jpos(1) == 2, "pair k = elements k, k + 8");
+  const u32 tpT = I0::tpos(t);  // 16 t
+  const bool active = grp < 3;
+  u64 qi = 0 - m.qinv;  // q^-1 mod 2^64 (subtractive REDC)
+  asm("" : "+s"(qi));
+  if (grp == 1) {
+#pragma unroll
+    for (int k = 0; k < kE / 2; ++k) {
+      const u32 i0 = own.idx(tpT | (2 * k)), i1 = own.idx(tpT | (2 * k + 1));
+      const u64 xa[4] = {rowlds[i0], rowlds[i1], rowlds[G::RS + i0], rowlds[G::RS + i1]};
+      const u64 b00 = rowlds[2 * G::RS + i0], b01 = rowlds[2 * G::RS + i1];
+      const u64 b10 = rowlds[3 * G::RS + i0], b11 = rowlds[3 * G::RS + i1];
+      const u64 ke[4] = {b10, rowlds[pair_bp_idx(1, k, t)], b00, rowlds[pair_bp_idx(0, k, t)]};
+      const u64 ko[4] = {b11, b10, b01, b00};
+      u64 tlo, thi;
+      dot_wide61<4>(xa, ke, tlo, thi);
+      v[k] = mont_redc_x(tlo, thi, q, qi);
+      dot_wide61<4>(xa, ko, tlo, thi);
+      v[k + kE / 2] = mont_redc_x(tlo, thi, q, qi);
+    }
+  } else if (active) {
+    const u64* A = rowlds + (grp == 2 ? G::RS : 0);
+    const u64* B = rowlds + (grp == 2 ? 3 * G::RS : 2 * G::RS);
+#pragma unroll
+    for (int k = 0; k < kE / 2; ++k) {
+      const u32 i0 = own.idx(tpT | (2 * k)), i1 = own.idx(tpT | (2 * k + 1));
+      const u64 a0 = A[i0], a1 = A[i1], b0 = B[i0], b1 = B[i1];
+      const u64 b1p = rowlds[grp == 2 ? pair_bp_idx(1, k, t) : pair_bp_idx(0, k, t)];
+      u64 tlo, thi;
+      mul2_wide61(a0, b0, a1, b1p, tlo, thi);
+      v[k] = mont_redc_x(tlo, thi, q, qi);
+      mul2_wide61(a0, b1, a1, b0, tlo, thi);
+      v[k + kE / 2] = mont_redc_x(tlo, thi, q, qi);
+    }
+  }
+  // inverse rows, first stage skipped: 3 stages on bits 1-3 from inputs below 2q, then bits 4-7
+  if (active)
+    round_compute<G::N2, 3, 1, false, kNotFinal, true, HR, 8, true, true, false, kElog, 2>(
+        v, tpT, ti, base, q, {0, 0}, {0, 0});
+  // the first store into this slot must wait until every group has read it for the tensor
+  lds_sync<ST>();
+  if (active) own.template store<I0>(v, tpT);
+  lds_sync<SY>();
+  if (active) {
+    const u32 tp = I1::tpos(t);
+    own.template load<I1>(v, tp);
+    round_compute<G::N2, 4, 4, false, kNotFinal, true, HR>(v, tp, ti, base, q, {0, 0}, {0, 0});
+    const GView<1, kHmNT> gout{d + ((u64)b * 3 + grp) * limbN + loc, 0};
+    gout.template store<I1>(v, tp);
+  }
+}
+
 // S9 (N = 2^16, after k_hm_col9): the forward rows are the 512 x 128 split's 7-stage rows, two
 // per 256-word row (its 16 threads: 8 per half), with twf the d_tw_fwd9 layout; the tensor and the
 // inverse are unchanged (the forward's last values go to LDS in its own layout, the tensor reads
@@ -1051,7 +1238,14 @@ __global__ FHE_KATTR void k_hommult_row(const u64* __restrict__ x,
   using H = HmGeo<LOGN>;
   using Rd = Rounds<G::N2>;
   constexpr u64 N = 1ull << LOGN;
-  __shared__ u64 lds[H::ROWS * H::ROWW];
+  // lz16 contexts after k_hm_col9: the pair form (hm_row_pairs), one stage fewer on either side of
+  // the tensor.  Every other instantiation runs the full stages below.
+  constexpr bool PAIR = S9 && HR == 16;
+  __shared__ u64 lds[H::ROWS * (PAIR ? kPairRoww : H::ROWW)];
+  if constexpr (PAIR) {
+    hm_row_pairs<LOGN>(lds, x, d, nlimbs, limb0, twf, twi, mods);
+    return;
+  }
   u32 l, rest;
   xcd_limb_split(blockIdx.x, nlimbs, gridDim.x / nlimbs, l, rest);
   // tile fastest: an XCD's workgroups stream each poly-limb's rows front to back (DRAM page
@@ -2057,6 +2251,20 @@ int hommult_dispatch(const fhe_ctx* c, u64* d, const u64* a, const u64* b, u32 b
   // forward rows one stage shorter); other sizes 8 + 8 (log N / 2 each)
   bool split9 = false;
   if constexpr (LOGN == 16 && HD != 2) split9 = c->d_tw_fwd9 != nullptr;
+  // the column inverse's fold: N^-1 R (entries 2, 3 of d_nfold: the Montgomery tensor left a factor
+  // R^-1) on every path that runs the full stages; 2 N^-1 R after the pair form of the row kernel
+  // (HD = 16 after k_hm_col9), whose inverse rows skip the stage that doubles
+  const ulonglong2* nf = c->d_nfold + 2;
+  if constexpr (LOGN == 16 && HD == 16) {
+    if (split9) {
+      // the pair tensor's 4-term sums stay below q 2^64 because q < 2^60 (16 q^2 < q 2^64)
+      if (!c->lz16 || !c->d_nfold_pair) {
+        set_error("hommult: the pair tensor needs an lz16 context (every modulus below 2^60)");
+        return kUnsupported;
+      }
+      nf = c->d_nfold_pair;
+    }
+  }
   if (split9) {
     if constexpr (LOGN == 16 && HD != 2) {
       const u64 i9 = (u64)batch * 4 * nlimbs * kC9Tiles;
@@ -2077,11 +2285,10 @@ int hommult_dispatch(const fhe_ctx* c, u64* d, const u64* a, const u64* b, u32 b
     prof_mark(s, "hm_row_tensor");
   }
   const u64 ii = (u64)batch * 3 * nlimbs * G::TILES_C;
-  // the Montgomery tensor left a factor R^-1: fold R in with N^-1 (entries 2, 3 of d_nfold)
   k_ntt_col<LOGN, false, inv_h(HD), kHmNT, kHmNT>
       <<<item_grid(ii),
          G::THR_C, 0, s>>>(d, nullptr, d, nlimbs, limb0, flat_map(limbN), (u32)ii, c->d_tw_inv,
-                           c->d_nfold + 2, c->d_mods);
+                           nf, c->d_mods);
   prof_mark(s, "hm_col_inv");
   return kOk;
 }
