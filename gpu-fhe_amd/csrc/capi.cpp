@@ -291,8 +291,8 @@ int fhe_keyswitch_shard(const fhe_ctx* c, uint64_t* ks0, uint64_t* ks1, const ui
   int rc = check_window(c, limb0, nlimbs, c ? c->L : 0, "fhe_keyswitch_shard");
   if (rc) return rc;
   if ((rc = ensure_ws(c, keyswitch_workspace_bytes(c, nlimbs, batch), &ws, hs(s)))) return rc;
-  return launch_keyswitch_shard(c, ks0, ks1, c_all, d2_own, evk_b, evk_a, limb0, nlimbs, batch,
-                                ws, hs(s));
+  return launch_keyswitch_shard(c, ks0, ks1, CAll::contiguous(c_all, c->L, c->n), d2_own, evk_b,
+                                evk_a, limb0, nlimbs, batch, ws, hs(s));
 }
 
 // level in [1, L] for the *_level entry points (a null context fails in check_window first)
@@ -326,22 +326,15 @@ int fhe_keyswitch_level(const fhe_ctx* c, uint64_t* ks0, uint64_t* ks1, const ui
     return rc;
   const uint32_t pass = ks_pass_batch(c, batch);  // Infinity-Cache-sized passes
   // the level's own regions: never more than fhe_keyswitch_workspace(ctx, L, pass)
-  const size_t bytes = keyswitch_workspace_bytes(c, level, pass, level);
-  if ((rc = ensure_ws(c, bytes, &ws, hs(s)))) return rc;
+  const KsPlan p = ks_plan_level(c, level, pass);
+  if ((rc = ensure_ws(c, p.bytes(), &ws, hs(s)))) return rc;
   // c_all = INTT(d2) of one pass lives at the tail of the workspace (out of place: no copy of d2)
-  const size_t call = (size_t)pass * ct_words * sizeof(uint64_t);
-  uint64_t* c_all = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + bytes - call);
-  // a prepared input when the fused ModUp applies: the INTT folds (D^_k)^-1 into its last stage
-  const bool prep = ks_prepared(c);
-  CAll src = CAll::contiguous(c_all, level, c->n);
-  src.scaled = prep;
+  uint64_t* c_all = static_cast<uint64_t*>(ws) + p.call;
+  CAll src{};
   for (uint32_t b0 = 0; b0 < batch; b0 += pass) {
     const uint32_t bn = std::min(pass, batch - b0);
     const uint64_t off = (uint64_t)b0 * ct_words;
-    if ((rc = launch_ntt_strided(c, false, d2 + off, ct_words, c_all, ct_words, bn, 0, level, hs(s),
-                                 prep ? ks_level_nfold_up(c, level) : nullptr,
-                                 prep && ks_split30(c))))
-      return rc;
+    if ((rc = ks_input_intt(c, p, d2 + off, ct_words, c_all, ct_words, bn, hs(s), &src))) return rc;
     if ((rc = launch_keyswitch_shard(c, ks0 + off, ks1 + off, src, d2 + off, evk_b, evk_a, 0, level,
                                      bn, ws, hs(s), nullptr, nullptr, level)))
       return rc;

@@ -77,11 +77,9 @@ int dist_intt_chunk(const fhe_ctx* ctx, const fhe_dist_plan& p, u32 k, const u64
   const u64 n = ctx->n;
   // the gathered d2 is the prepared ModUp input when the fused ModUp applies: each rank's INTT
   // folds (D^_k)^-1 of its limbs' digits into its last stage
-  const bool prep = ks_prepared(ctx);
-  return launch_ntt_strided(ctx, false, d2_own + (u64)b0 * p.nlimbs * n, (u64)p.nlimbs * n,
-                            gather + fhe_dist_plan_send_word(&p, b0, 0), (u64)p.width * n, bn,
-                            p.limb0, p.nlimbs, s, prep ? ctx->d_nfold_up : nullptr,
-                            prep && ks_split30(ctx));
+  return ks_input_intt(ctx, ks_plan(ks_shape(ctx), p.limb0, p.nlimbs, bn, 0),
+                       d2_own + (u64)b0 * p.nlimbs * n, (u64)p.nlimbs * n,
+                       gather + fhe_dist_plan_send_word(&p, b0, 0), (u64)p.width * n, bn, s);
 }
 
 // One chunk's local key-switch once its gather has landed.
@@ -92,7 +90,7 @@ int dist_ks_chunk(const fhe_ctx* ctx, const fhe_dist_plan& p, u32 k, u64* ks0, u
   fhe_dist_plan_chunk(&p, k, &b0, &bn);
   if (!p.nlimbs || !bn) return kOk;
   CAll call = chunk_call(p, gather, k);
-  call.scaled = ks_prepared(ctx);
+  call.scaled = ks_plan(ks_shape(ctx), p.limb0, p.nlimbs, bn, 0).prepared;  // dist_intt_chunk
   const u64 off = (u64)b0 * p.nlimbs * ctx->n;
   return launch_keyswitch_shard(ctx, ks0 + off, ks1 + off, call, d2_own + off, evk_b, evk_a,
                                 p.limb0, p.nlimbs, bn, kws, s);

@@ -433,13 +433,59 @@ int launch_mod_raise(const fhe_ctx* c, u64* out, const u64* in, u32 in_level, u3
   return kOk;
 }
 
+namespace {
+// Workspace layouts at `level` live Q-limbs (ws null: the size only): the regions are laid out for
+// that many, so the *_workspace_bytes, the layouts' ends at c->L, cover every level
+struct RotateWs {
+  u64* sc1;  // [batch][level][N] sigma(c1)
+  u64* sc0;  // [batch][level][N] sigma(c0)
+  u64* kws;  // the key-switch's own workspace (ks: its plan; the tail holds INTT(sigma(c1)))
+  KsPlan ks;
+  size_t bytes;
+};
+RotateWs rotate_ws(const fhe_ctx* c, void* ws, u32 level, u32 batch) {
+  const u64 ln = (u64)level * c->n;
+  WsCarve w{static_cast<u64*>(ws)};
+  RotateWs r;
+  r.sc1 = w.take(batch * ln);
+  r.sc0 = w.take(batch * ln);
+  r.ks = ks_plan_level(c, level, batch);
+  r.kws = w.take(r.ks.total);
+  r.bytes = w.bytes();
+  return r;
+}
+// The hoisted forms (the rotation sums; launch_rotate_hoisted takes the same regions), laid out
+// for the call's `level` live Q-limbs (L below) and its live digits: never more than the top level's
+struct RotSumWs {
+  u64* c_all;  // [batch][L][N] coefficient form of the c1 being ModUp'ed
+  u64* cadd;   // [2][batch][L][N]: the c0 sum, then the unrotated terms' c1 sum
+  u64* ydn;    // [2 batch][K][N] the fused ModDown's INTT output
+  // key-switch workspace: its ext region holds the NTT-form digits across the rotations, then the
+  // accumulators (ks: the plan of a hoisted step given ydn; the regions are every mode's)
+  u64* kws;
+  KsPlan ks;
+  u32 level;   // the live Q-limbs
+  size_t bytes;
+};
+RotSumWs rotsum_ws(const fhe_ctx* c, void* ws, u32 level, u32 batch) {
+  const u64 ln = (u64)level * c->n;
+  WsCarve carve{static_cast<u64*>(ws)};
+  RotSumWs w;
+  w.c_all = carve.take(batch * ln);
+  w.cadd = carve.take(2 * batch * ln);
+  w.ydn = carve.take(2 * batch * (u64)c->K * c->n);
+  w.ks = ks_plan_level(c, level, batch, kKsHoistInner, true);
+  w.kws = carve.take(w.ks.total);
+  w.level = level;
+  w.bytes = carve.bytes();
+  return w;
+}
+}  // namespace
+
 size_t rotate_workspace_bytes(const fhe_ctx* c, u32 batch) {
-  // sigma(c1) and sigma(c0) [batch][L][N], then the key-switch's own workspace
-  return 2 * (size_t)batch * c->L * c->n * sizeof(u64) + keyswitch_workspace_bytes(c, c->L, batch);
+  return rotate_ws(c, nullptr, c->L, batch).bytes;
 }
 
-// `level` Q-limbs (1 .. c->L) in in / out: the workspace regions are laid out for that many
-// (rotate_workspace_bytes, sized for c->L, covers every level).
 int launch_rotate(const fhe_ctx* c, u64* out, const u64* in, u32 galois_elt, const u64* rot_b,
                   const u64* rot_a, u32 level, u32 batch, void* ws, hipStream_t s) {
   if (c->K == 0) {
@@ -462,42 +508,29 @@ int launch_rotate(const fhe_ctx* c, u64* out, const u64* in, u32 galois_elt, con
     }
     return kOk;
   }
-  u64* sc1 = static_cast<u64*>(ws);  // [batch][L][N]
-  u64* sc0 = sc1 + batch * ln;
-  u64* kws = sc0 + batch * ln;
+  const RotateWs w = rotate_ws(c, ws, level, batch);
   int rc;
   // sigma(c0) is gathered by the ModDown finish itself where that is k_moddown_row
-  const bool gather0 = ks_fused(c);
+  const bool gather0 = w.ks.row_finish;
   if ((!gather0 &&
-       (rc = launch_automorphism(c, sc0, ln, in, 2 * ln, batch, 0, L, galois_elt, true, s))) ||
-      (rc = launch_automorphism(c, sc1, ln, in + ln, 2 * ln, batch, 0, L, galois_elt, true, s)))
+       (rc = launch_automorphism(c, w.sc0, ln, in, 2 * ln, batch, 0, L, galois_elt, true, s))) ||
+      (rc = launch_automorphism(c, w.sc1, ln, in + ln, 2 * ln, batch, 0, L, galois_elt, true, s)))
     return rc;
   // key-switch sigma(c1): its coefficient form goes to the tail of the key-switch workspace
-  const size_t kbytes = keyswitch_workspace_bytes(c, L, batch, level);
-  u64* c_all = reinterpret_cast<u64*>(reinterpret_cast<char*>(kws) + kbytes) - batch * ln;
-  const bool prep = ks_prepared(c);  // the INTT emits ModUp's scaled inputs
-  if ((rc = launch_ntt_strided(c, false, sc1, ln, c_all, ln, batch, 0, L, s,
-                               prep ? ks_level_nfold_up(c, level) : nullptr,
-                               prep && ks_split30(c))))
-    return rc;
-  CAll call = CAll::contiguous(c_all, L, n);
-  call.scaled = prep;
+  CAll call{};
+  if ((rc = ks_input_intt(c, w.ks, w.sc1, ln, w.kws + w.ks.call, ln, batch, s, &call))) return rc;
   // out = (sigma(c0) + ks0, ks1) straight out of the key-switch's ModDown finish (KsEpilogue)
   KsEpilogue ep;
   ep.out_bs = 2 * ln;
-  ep.add0 = gather0 ? in : sc0;
+  ep.add0 = gather0 ? in : w.sc0;
   ep.add_bs = gather0 ? 2 * ln : ln;
   ep.add_gal = gather0 ? galois_elt : 0;
-  return launch_keyswitch_shard(c, out, out + ln, call, sc1, rot_b, rot_a, 0, L, batch, kws, s,
-                                &ep, nullptr, level);
+  return launch_keyswitch_shard(c, out, out + ln, call, w.sc1, rot_b, rot_a, 0, L, batch, w.kws,
+                                s, &ep, nullptr, level);
 }
 
 size_t rotate_hoisted_workspace_bytes(const fhe_ctx* c, u32 batch) {
-  // c1 (NTT form) and its coefficient form, sigma(c0) [batch][L][N], then the key-switch workspace
-  // (its ext region holds the NTT-form digits across the rotations)
-  // (+ [2 batch][K][N] for the fused ModDown's INTT output)
-  return (3 * (size_t)c->L + 2 * (size_t)c->K) * batch * c->n * sizeof(u64) +
-         keyswitch_workspace_bytes(c, c->L, batch);
+  return rotsum_ws(c, nullptr, c->L, batch).bytes;
 }
 
 // Hoisted rotations (Halevi-Shoup): the ModUp of c1 -- INTT, base conversion, NTT of every digit,
@@ -530,23 +563,17 @@ int launch_rotate_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* 
   if (batch == 0 || count == 0) return kOk;
   const u32 L = level;  // the live Q-limbs
   const u64 n = c->n, ln = (u64)L * n;
-  u64* c1 = static_cast<u64*>(ws);  // [batch][L][N] NTT form
-  u64* c_all = c1 + batch * ln;     // [batch][L][N] coefficient form
-  u64* sc0 = c_all + batch * ln;    // [batch][L][N]
-  u64* ydn = sc0 + batch * ln;      // [2 batch][K][N]
-  u64* kws = ydn + 2 * batch * (u64)c->K * n;
+  // the rotation sums' layout, its three [batch][L][N] regions taken as c1 (NTT form), its
+  // coefficient form and sigma(c0)
+  const RotSumWs w = rotsum_ws(c, ws, level, batch);
+  u64 *c1 = w.c_all, *c_all = w.cadd, *sc0 = w.cadd + batch * ln, *kws = w.kws;
   FHE_HIP_CHECK(hipMemcpy2DAsync(c1, ln * sizeof(u64), in + ln, 2 * ln * sizeof(u64),
                                  ln * sizeof(u64), batch, hipMemcpyDeviceToDevice, s));
   int rc;
   // prepared INTT (the ModUp digits' (D^_k)^-1 folded in) where the hoisted ModUp takes the fused
-  // conversion pass (rns.hip hoist_up)
-  const bool prep = ks_prepared(c);
-  if ((rc = launch_ntt_strided(c, false, c1, ln, c_all, ln, batch, 0, L, s,
-                               prep ? ks_level_nfold_up(c, level) : nullptr,
-                               prep && ks_split30(c))))
-    return rc;
-  CAll call = CAll::contiguous(c_all, L, n);
-  call.scaled = prep;
+  // conversion pass (KsPlan::hoist_up)
+  CAll call{};
+  if ((rc = ks_input_intt(c, w.ks, c1, ln, c_all, ln, batch, s, &call))) return rc;
   KsHoist up;
   up.modup_only = true;
   if ((rc = launch_keyswitch_shard(c, nullptr, nullptr, call, c1, nullptr, nullptr, 0, L, batch,
@@ -556,10 +583,10 @@ int launch_rotate_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* 
     u64* o = out + (u64)r * batch * 2 * ln;
     KsHoist h;
     h.galois = galois[r];
-    h.ydn = ydn;
+    h.ydn = w.ydn;
     KsEpilogue ep;
     ep.out_bs = 2 * ln;
-    if (ks_hoist_fused_down(c)) {  // the ModDown finish reads c0 through sigma itself
+    if (w.ks.row_finish) {  // the ModDown finish reads c0 through sigma itself
       ep.add0 = in;
       ep.add_bs = 2 * ln;
       ep.add_gal = galois[r];
@@ -577,34 +604,10 @@ int launch_rotate_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u32* 
 }
 
 size_t rotate_sum_hoisted_workspace_bytes(const fhe_ctx* c, u32 batch) {
-  // c1's coefficient form [batch][L][N], the c0 / c1 addends [2][batch][L][N], the fused ModDown's
-  // INTT output [2 batch][K][N], then the key-switch workspace (ext digits, accumulators)
-  return (3 * (size_t)c->L + 2 * (size_t)c->K) * batch * c->n * sizeof(u64) +
-         keyswitch_workspace_bytes(c, c->L, batch);
+  return rotsum_ws(c, nullptr, c->L, batch).bytes;
 }
 
 namespace {
-// The rotation sums' workspace regions (rotate_sum_hoisted_workspace_bytes), laid out for the
-// call's `level` live Q-limbs (L below) and its ceil(level / alpha) live digits: never more than
-// the top level's
-struct RotSumWs {
-  u64* c_all;  // [batch][L][N] coefficient form of the c1 being ModUp'ed
-  u64* cadd;   // [2][batch][L][N]: the c0 sum, then the unrotated terms' c1 sum
-  u64* ydn;    // [2 batch][K][N] the fused ModDown's INTT output
-  u64* kws;    // key-switch workspace: ext [dnum][batch][L + K][N], then the accumulators
-  u32 level;   // the live Q-limbs
-};
-RotSumWs rotsum_ws(const fhe_ctx* c, void* ws, u32 level, u32 batch) {
-  const u64 ln = (u64)level * c->n;
-  RotSumWs w;
-  w.c_all = static_cast<u64*>(ws);
-  w.cadd = w.c_all + batch * ln;
-  w.ydn = w.cadd + 2 * batch * ln;
-  w.kws = w.ydn + 2 * batch * (u64)c->K * c->n;
-  w.level = level;
-  return w;
-}
-
 int rotsum_check(const fhe_ctx* c, u32 level, u32 count, const u32* galois, const char* who) {
   if (c->K == 0) {
     set_error(std::string(who) + ": context has no special primes (K = 0)");
@@ -632,23 +635,15 @@ int rotsum_check(const fhe_ctx* c, u32 level, u32 count, const u32* galois, cons
 }
 
 // ModUp of in's c1 ([batch][2][L][N], NTT form) into the ext region at kws (w.kws, or another
-// region of ext_words(c, level, batch) words: a ModUp-only key-switch writes nothing past its digits):
+// region of w.ks.ext_words() words: a ModUp-only key-switch writes nothing past its digits):
 // the prepared INTT (the fused hoisted ModUp's scaled inputs) and the hoisted ModUp (rns.hip,
 // modup_only)
-u64 ext_words(const fhe_ctx* c, u32 level, u32 batch) {
-  return (u64)ks_level_digits(c, level) * batch * (level + c->K) * c->n;
-}
 int rotsum_modup(const fhe_ctx* c, const u64* in, u32 batch, const RotSumWs& w, hipStream_t s,
                  u64* kws = nullptr) {
   const u32 L = w.level;
   const u64 ln = (u64)L * c->n;
-  const bool prep = ks_prepared(c);
-  if (int rc = launch_ntt_strided(c, false, in + ln, 2 * ln, w.c_all, ln, batch, 0, L, s,
-                                  prep ? ks_level_nfold_up(c, L) : nullptr,
-                                  prep && ks_split30(c)))
-    return rc;
-  CAll call = CAll::contiguous(w.c_all, L, c->n);
-  call.scaled = prep;
+  CAll call{};
+  if (int rc = ks_input_intt(c, w.ks, in + ln, 2 * ln, w.c_all, ln, batch, s, &call)) return rc;
   KsHoist up;
   up.modup_only = true;
   return launch_keyswitch_shard(c, nullptr, nullptr, call, in + ln, nullptr, nullptr, 0, L, batch,
@@ -659,7 +654,7 @@ int rotsum_modup(const fhe_ctx* c, const u64* in, u32 batch, const RotSumWs& w, 
 // a term is rotated): the accumulators and cadd get the sums (flags: kRotSumC1)
 int rotsum_pass(const fhe_ctx* c, const u64* in, const RotSumTerms& tm, int flags, u32 batch,
                 const RotSumWs& w, hipStream_t s) {
-  const u32 L = w.level, rows = L + c->K, dl = ks_level_digits(c, L);
+  const u32 L = w.level, rows = w.ks.rows, dl = w.ks.digits;
   const u64 n = c->n;
   // the top-level keys and plaintexts in place: digit stride (c->L + K) N, special rows from c->L
   const u64 kds = (u64)(c->L + c->K) * n;
@@ -668,8 +663,8 @@ int rotsum_pass(const fhe_ctx* c, const u64* in, const RotSumTerms& tm, int flag
   const u64 blocks = (u64)rows * (n / kThreads);
   const u64 grid = (blocks + 7) / 8 * 8 * ((batch + kRotSumBC - 1) / kRotSumBC);
   if (int rc = check_grid(grid, kThreads, 1, 1, "rotate_sum")) return rc;
-  u64* acc = ks_acc_region(c, w.kws, L, batch, L);
-  const u64 acc_ws = (u64)batch * rows * n;
+  u64* acc = w.kws + w.ks.acc;
+  const u64 acc_ws = w.ks.acc_stride();
   const u64* ext = w.kws;
   // the live digits choose the instantiation; FAST stays a property of the context (fast above);
   // LVL below the top level only
@@ -755,13 +750,13 @@ int launch_rotate_sum_hoisted(const fhe_ctx* c, u64* out, const u64* in, const u
 
 size_t rotate_sum_multi_workspace_bytes(const fhe_ctx* c, u32 count, u32 batch) {
   // the rotation sum's workspace, then the ModUp digits of every rotated term past the first
-  return rotate_sum_hoisted_workspace_bytes(c, batch) +
-         (size_t)(count > 1 ? count - 1 : 0) * ext_words(c, c->L, batch) * sizeof(u64);
+  const RotSumWs w = rotsum_ws(c, nullptr, c->L, batch);
+  return w.bytes + (size_t)(count > 1 ? count - 1 : 0) * w.ks.ext_words() * sizeof(u64);
 }
 
 namespace {
 // The giant-step sum: every rotated term's ModUp into its own digit region (the first in w's ext
-// region, the others in `extra`, ext_words of w's level each), then ONE k_rot_sum pass over all the terms (each
+// region, the others in `extra`, w.ks.ext_words() each), then ONE k_rot_sum pass over all the terms (each
 // with its own ciphertext and digits, no plaintext: the accumulators are written once) and ONE
 // ModDown.
 int rotsum_multi(const fhe_ctx* c, u64* out, const u64* const* cts, const u32* galois,
@@ -777,7 +772,7 @@ int rotsum_multi(const fhe_ctx* c, u64* out, const u64* const* cts, const u32* g
     tm.pt[r] = nullptr;
     tm.in[r] = cts[r];
     if (galois[r] == 1) continue;
-    u64* region = nrot == 0 ? w.kws : extra + (u64)(nrot - 1) * ext_words(c, w.level, batch);
+    u64* region = nrot == 0 ? w.kws : extra + (u64)(nrot - 1) * w.ks.ext_words();
     if (int rc = rotsum_modup(c, cts[r], batch, w, s, region)) return rc;
     tm.ext[r] = region;
     ++nrot;
@@ -799,7 +794,7 @@ int launch_rotate_sum_multi(const fhe_ctx* c, u64* out, const u64* const* cts, c
   if (int rc = rotsum_check(c, level, count, galois, "rotate_sum_multi")) return rc;
   if (batch == 0 || count == 0) return kOk;
   // the extra digit regions start where the top level's do (past the rotation sum's top-level
-  // workspace) and are a level's ext_words each, so they end within the top-level size
+  // workspace) and are a level's digits region each, so they end within the top-level size
   u64* extra = reinterpret_cast<u64*>(static_cast<char*>(ws) +
                                       rotate_sum_hoisted_workspace_bytes(c, batch));
   return rotsum_multi(c, out, cts, galois, rot_b, rot_a, count, batch,

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "host_tables.hpp"
+#include "ks_plan.hpp"
 #include "modarith.hpp"
 
 namespace fhe {
@@ -257,26 +258,37 @@ int launch_ks_row_fin(const fhe_ctx* c, const KsFinArgs& a, hipStream_t s);
 // Hoisted rotations (galois.hip launch_rotate_hoisted): modup_only runs ModUp alone and leaves the
 // NTT-form digits in the workspace's ext region; otherwise the key-switch skips ModUp and reads
 // those digits (and d2_own) through sigma_galois inside the inner product (unfused kernels).
-// Whether a key-switch finishes in k_moddown_row (which can gather its addend, add_gal)
-inline bool ks_fused(const fhe_ctx* c) { return c->dnum <= 4 && !c->wide; }
-// The hoisted rotation's inner step takes the fused ModDown (whose finish can gather sigma(c0))
-inline bool ks_hoist_fused_down(const fhe_ctx* c) { return c->K <= 4 && c->dnum <= 4 && !c->wide; }
 struct KsHoist {
   bool modup_only = false;
   u32 galois = 0;
   u64* ydn = nullptr;  // [2 batch][K][N] scratch for the fused ModDown (the ext region is taken)
-  // the caller has filled the accumulators (ks_acc_region) itself: ModDown only (the rotation
+  // the caller has filled the accumulators (KsPlan::acc) itself: ModDown only (the rotation
   // sum, galois.hip launch_rotate_sum_hoisted)
   bool acc_ready = false;
+  KsMode mode() const { return modup_only ? kKsModUpOnly : acc_ready ? kKsAccReady : kKsHoistInner; }
 };
-// The key-switch workspace's regions (keyswitch_workspace_bytes): ext [dnum][batch][rows][N], then
-// the accumulators acc [2][batch][rows][N], rows = nlimbs + K
-// (level != 0: a level call's live digits in place of dnum)
-inline u32 ks_level_digits(const fhe_ctx* c, u32 level);
-inline u64* ks_acc_region(const fhe_ctx* c, void* ws, u32 nlimbs, u32 batch, u32 level = 0) {
-  const u64 dl = level ? ks_level_digits(c, level) : c->dnum;
-  return static_cast<u64*>(ws) + dl * batch * (nlimbs + c->K) * c->n;
+// The plan of a key-switch on this context (ks_plan.hpp): the paths launch_keyswitch_shard takes
+// for the same arguments and its workspace regions, for the callers that must match them.
+inline KsShape ks_shape(const fhe_ctx* c) {
+  return KsShape{c->L, c->K, c->dnum, c->alpha, c->n, c->wide, c->lz16};
 }
+// the single-device form over the first `level` Q-limbs (1 .. L)
+inline KsPlan ks_plan_level(const fhe_ctx* c, u32 level, u32 batch, KsMode mode = kKsFull,
+                            bool ydn = false) {
+  return ks_plan(ks_shape(c), 0, level, batch, level, mode, ydn);
+}
+// Consecutive regions of a workspace: take(words) returns the next one.  A null base only measures,
+// so a *_workspace_bytes (the end at level L) and its launcher share one layout function.
+struct WsCarve {
+  u64* base;
+  u64 words = 0;
+  u64* take(u64 w) {
+    u64* p = base ? base + words : nullptr;
+    words += w;
+    return p;
+  }
+  size_t bytes() const { return words * sizeof(u64); }
+};
 struct ModDownRowArgs {
   const u64* conv;
   u64* ks0;
@@ -347,13 +359,10 @@ int launch_conj(const fhe_ctx* c, bool merge, u64* re, u64* im, const u64* ct, c
 
 // ---- launchers (rns.hip) --------------------------------------------------------------
 // Per-rank body of the hybrid key-switch (SURVEY.md §8a', §8e) over `batch` ciphertexts sharing
-// one key: c_all [batch][L][N] coefficient form of the whole d2 (all-gathered), d2_own
-// [batch][nlimbs][N] NTT form of this rank's Q-limbs [limb0, limb0 + nlimbs), evk_b/evk_a
-// [dnum][nlimbs + K][N] NTT form (own Q-limbs then P).  ks0/ks1 [batch][nlimbs][N] NTT form.
-int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const u64* c_all,
-                           const u64* d2_own, const u64* evk_b, const u64* evk_a, u32 limb0,
-                           u32 nlimbs, u32 batch, void* ws, hipStream_t s);
-// Where a key-switch finds the coefficient-form d2 of every Q-limb: element (b, l, i) at
+// one key (launch_keyswitch_shard below): call, the coefficient form of the whole d2
+// (all-gathered), d2_own [batch][nlimbs][N] NTT form of this rank's Q-limbs [limb0, limb0 + nlimbs),
+// evk_b/evk_a [dnum][nlimbs + K][N] NTT form (own Q-limbs then P).  ks0/ks1 [batch][nlimbs][N] NTT
+// form.  Where it finds the coefficient-form d2 of every Q-limb: element (b, l, i) at
 // ptr + b bs + (l / lpr) rs + (l % lpr) N + i.  Contiguous [batch][L][N]: lpr = L, bs = L N.
 // The rank-major output of an all-gather over G ranks of c = ceil(L / G) limbs each,
 // [G][batch][c][N] (the last ranks' blocks padded): lpr = c, rs = batch c N, bs = c N.
@@ -371,15 +380,21 @@ struct CAll {
   // it folded the factor into its last stage, d_nfold_up), so ModUp's scaling pass is skipped
   bool scaled = false;
 };
-// Whether a key-switch on this context takes the fused ModUp (conversion inside the column pass),
-// which can read a prepared (pre-scaled) input: dnum <= 4, digits of <= 4 limbs, q < 2^61.
-inline bool ks_prepared(const fhe_ctx* c) {
-  return c->K > 0 && c->dnum <= 4 && c->alpha <= 4 && !c->wide;
+// The INTT of d2 ahead of the key-switch p plans: src (poly stride sps) -> dst (poly stride dps),
+// p's limb window of `polys` ciphertexts; a prepared input where the context takes one.  *call: the
+// contiguous view of dst (dps = nlimbs N) with `scaled` set; a caller with another layout
+// (dist.cpp's gather) sets `scaled` = p.prepared on its own view.
+inline int ks_input_intt(const fhe_ctx* c, const KsPlan& p, const u64* src, u64 sps, u64* dst,
+                         u64 dps, u32 polys, hipStream_t s, CAll* call = nullptr) {
+  const ulonglong2* tab =
+      p.partial ? c->d_lvl_nfold_up + (size_t)p.level * 4 * (c->L + c->K) : c->d_nfold_up;
+  if (call) {
+    *call = CAll::contiguous(dst, p.nlimbs, c->n);
+    call->scaled = p.prepared;
+  }
+  return launch_ntt_strided(c, false, src, sps, dst, dps, polys, p.limb0, p.nlimbs, s,
+                            p.prepared ? tab : nullptr, p.prepared && p.split30);
 }
-// The fused conversions' source format (k_modup_col): lz16 contexts (every q < 2^60) read plain
-// residues (dot_wide61 on 32-bit halves); the others read Sum30's 30-bit pieces (split30), which
-// the INTTs and k_modup_scale feeding them emit directly.
-inline bool ks_split30(const fhe_ctx* c) { return !c->lz16; }
 
 // The single-device key-switch paths (fhe_keyswitch, mul-relin, rotate) run a batch in passes of
 // at most this many bytes of INTT(d2), the size of the Infinity Cache: ModUp then reads its
@@ -398,22 +413,13 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
                            u32 level = 0);
 // level != 0 (then limb0 = 0, nlimbs = level): the key-switch over the first `level` Q-limbs with
 // the top-level digit width and the top-level key [dnum][L + K][N] read in place (key rows
-// {0 .. level-1} u {L .. L+K-1} of the digits j < ks_level_digits); call holds `level` limbs,
-// prepared with ks_level_nfold_up's table.  level == L is the top-level call itself.  The three
-// hoist modes (KsHoist) run over the same live limbs, digits and rows.
-inline u32 ks_level_digits(const fhe_ctx* c, u32 level) {
-  return (level + c->alpha - 1) / c->alpha;
+// {0 .. level-1} u {L .. L+K-1} of the live digits, KsPlan::digits); call holds `level` limbs,
+// prepared by ks_input_intt.  level == L is the top-level call itself.  The three hoist modes
+// (KsHoist) run over the same live limbs, digits and rows.
+// The plan's total (level != 0: the regions of a level call, never more than the top level's)
+inline size_t keyswitch_workspace_bytes(const fhe_ctx* c, u32 nlimbs, u32 batch, u32 level = 0) {
+  return ks_plan(ks_shape(c), 0, nlimbs, batch, level).bytes();
 }
-// whether level's last digit is partial (its constants come from the d_lvl_* tables)
-inline bool ks_level_partial(const fhe_ctx* c, u32 level) {
-  return level < c->L && level % c->alpha != 0;
-}
-inline const ulonglong2* ks_level_nfold_up(const fhe_ctx* c, u32 level) {
-  return ks_level_partial(c, level) ? c->d_lvl_nfold_up + (size_t)level * 4 * (c->L + c->K)
-                                    : c->d_nfold_up;
-}
-// (level != 0: the regions of a level call, never more than the top level's)
-size_t keyswitch_workspace_bytes(const fhe_ctx* c, u32 nlimbs, u32 batch, u32 level = 0);
 // The key-switch aliasing rule (include/fhecore.h): each output span (out_words from ks0 / ks1)
 // either is d2 itself (same start, the contiguous layout: `contiguous`, out_words == d2_words) or
 // does not overlap d2's d2_words; with contiguous outputs ks0 and ks1 must not overlap each other

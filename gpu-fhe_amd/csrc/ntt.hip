@@ -1542,7 +1542,7 @@ __global__ __launch_bounds__(kColThreads) __attribute__((amdgpu_waves_per_eu(
     }
   } else {
     // the constants' 30-bit pieces (Sum30: four v_mad_u64_u32 per term; sources arrive pre-split,
-    // ks_split30)
+    // KsPlan::split30)
     u64 h2[TG][S], h2w[TG][S];
 #pragma unroll
     for (u32 g = 0; g < TG; ++g) {

@@ -52,19 +52,39 @@ __global__ __launch_bounds__(kTensorThreads) void k_tensor_ntt(u64* __restrict__
   *reinterpret_cast<vu64x2*>(d2 + bt * ln + (u64)l * n + c) = o2;
 }
 
+// The workspace of launch_mul_relin at `level` live Q-limbs (ws null: the size only)
+struct MulRelinWs {
+  u64 *d, *rl;  // [batch][2][level][N] each: d0, d1; the relinearised ct before the rescale
+  // [batch][level][N] d2, NTT form, the key-switch's input (its finish may run in the same kernel
+  // as its reads of d2, k_ks_row_fin, so d2 cannot park in the output)
+  u64* d2;
+  u64* rws;  // the rescale's own workspace
+  u64* kws;  // the key-switch's workspace (ks: its plan; the tail holds INTT(d2))
+  KsPlan ks;
+  size_t bytes;
+};
+MulRelinWs mul_relin_ws(const fhe_ctx* c, void* ws, u32 level, u32 batch) {
+  const u64 ln = (u64)level * c->n;
+  WsCarve w{static_cast<u64*>(ws)};
+  MulRelinWs r;
+  r.d = w.take(2 * batch * ln);
+  r.rl = w.take(2 * batch * ln);
+  r.d2 = w.take(batch * ln);
+  r.rws = w.take(rescale_workspace_bytes(c, 2 * batch, level) / sizeof(u64));
+  r.ks = ks_plan_level(c, level, batch);
+  r.kws = w.take(r.ks.total);
+  r.bytes = w.bytes();
+  return r;
+}
+
 }  // namespace
 
 size_t mul_relin_workspace_bytes(const fhe_ctx* c, u32 batch) {
-  const size_t ln = (size_t)c->L * c->n * sizeof(u64);
-  // d0, d1 [2], relinearised ct before the rescale [2], d2 [1] (the key-switch's finish may run in
-  // the same kernel as its reads of d2, k_ks_row_fin, so d2 cannot park in the output), the
-  // rescale's own [2 L N] workspace, the key-switch's workspace (its tail holds INTT(d2))
-  return (size_t)batch * ln * (2 + 2 + 1) + rescale_workspace_bytes(c, 2 * batch, c->L) +
-         keyswitch_workspace_bytes(c, c->L, batch);
+  return mul_relin_ws(c, nullptr, c->L, batch).bytes;
 }
 
-// `level` Q-limbs (1 .. c->L) in a, b and out: the workspace regions below are laid out for that
-// many, so mul_relin_workspace_bytes (sized for c->L) covers every level.
+// `level` Q-limbs (1 .. c->L) in a, b and out: the workspace regions are laid out for that many,
+// so mul_relin_workspace_bytes (sized for c->L) covers every level.
 int launch_mul_relin(const fhe_ctx* c, u64* out, const u64* a, const u64* b, const u64* evk_b,
                      const u64* evk_a, u32 level, u32 batch, bool rescale, void* ws,
                      hipStream_t s) {
@@ -93,12 +113,8 @@ int launch_mul_relin(const fhe_ctx* c, u64* out, const u64* a, const u64* b, con
     }
     return kOk;
   }
-  u64* d = static_cast<u64*>(ws);        // [batch][2][L][N]: d0, d1
-  u64* rl = d + 2 * batch * ln;          // [batch][2][L][N] relinearised, before the rescale
-  u64* d2 = rl + 2 * batch * ln;         // [batch][L][N] d2, NTT form, the key-switch's input
-  u64* rws = d2 + batch * ln;            // rescale workspace
-  u64* kws = reinterpret_cast<u64*>(reinterpret_cast<char*>(rws) +
-                                    rescale_workspace_bytes(c, 2 * batch, L));
+  const MulRelinWs w = mul_relin_ws(c, ws, level, batch);
+  u64 *d = w.d, *d2 = w.d2;
   const u64 tb = n / 2 / kTensorThreads;  // N >= 2^10: whole blocks of coefficient pairs
   if (int rc = check_grid(tb, kTensorThreads, L, batch, "tensor_ntt")) return rc;
   const dim3 g((u32)tb, L, batch);
@@ -107,30 +123,23 @@ int launch_mul_relin(const fhe_ctx* c, u64* out, const u64* a, const u64* b, con
   prof_mark(s, "tensor_ntt");
   // d2 = d[b][2]: gather to a contiguous [batch][L][N] operand for the key-switch (its INTT lands
   // at the tail of the key-switch workspace, as in fhe_keyswitch)
-  const size_t kbytes = keyswitch_workspace_bytes(c, L, batch, level);
-  u64* c_all = reinterpret_cast<u64*>(reinterpret_cast<char*>(kws) + kbytes) - batch * ln;
   int rc;
-  const bool prep = ks_prepared(c);  // the INTT emits ModUp's scaled inputs
-  if ((rc = launch_ntt_strided(c, false, d2, ln, c_all, ln, batch, 0, L, s,
-                               prep ? ks_level_nfold_up(c, level) : nullptr,
-                               prep && ks_split30(c))))
-    return rc;
-  CAll call = CAll::contiguous(c_all, L, n);
-  call.scaled = prep;
+  CAll call{};
+  if ((rc = ks_input_intt(c, w.ks, d2, ln, w.kws + w.ks.call, ln, batch, s, &call))) return rc;
   // the relinearised ciphertext (d0 + ks0, d1 + ks1) straight out of the ModDown finish
   // ([batch][2][L][N] outputs and addends, 2 L N apart per ciphertext)
-  u64* dst = rescale ? rl : out;
+  u64* dst = rescale ? w.rl : out;
   KsEpilogue ep;
   ep.out_bs = 2 * ln;
   ep.add0 = d;
   ep.add1 = d + ln;
   ep.add_bs = 2 * ln;
-  if ((rc = launch_keyswitch_shard(c, dst, dst + ln, call, d2, evk_b, evk_a, 0, L, batch, kws, s,
-                                   &ep, nullptr, level)))
+  if ((rc = launch_keyswitch_shard(c, dst, dst + ln, call, d2, evk_b, evk_a, 0, L, batch, w.kws,
+                                   s, &ep, nullptr, level)))
     return rc;
   prof_mark(s, "relin_keyswitch");
   if (rescale) {
-    if ((rc = launch_rescale(c, out, rl, 2 * batch, L, true, rws, s))) return rc;
+    if ((rc = launch_rescale(c, out, w.rl, 2 * batch, L, true, w.rws, s))) return rc;
     prof_mark(s, "rescale");
   }
   return kOk;

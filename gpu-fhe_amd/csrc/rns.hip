@@ -237,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void k_modup_scale(const u64* __restrict_
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   const u64 q = mods[mod0 + k].q;
   const ulonglong2 w = inv[k];
-  // split30: k_modup_col reads its sources as Sum30 pieces on non-lz16 contexts (ks_split30)
+  // split30: k_modup_col reads its sources as Sum30 pieces on non-lz16 contexts (KsPlan::split30)
   const u64 v = csub(shoup_lazy(in[(u64)b * in_bs + koff.o[k] + i], w.x, w.y, q), q);
   y[((u64)b * S + k) * n + i] = split ? split30(v) : v;
 }
@@ -432,21 +432,235 @@ int build_rns_tables(fhe_ctx* c) {
   return kOk;
 }
 
-size_t keyswitch_workspace_bytes(const fhe_ctx* c, u32 nlimbs, u32 batch, u32 level) {
-  const u64 rows = nlimbs + c->K;
-  // ext [dnum][batch][rows][N] + acc [2][batch][rows][N] + conv [2][batch][nlimbs][N]
-  // + y [batch][alpha][N] (fused ModUp) + c_all [batch][L][N] (single-device form, at the tail)
-  // (a level call: its live digits and its own limbs in place of dnum and L)
-  const u64 dl = level ? ks_level_digits(c, level) : c->dnum, cl = level ? level : c->L;
-  return (u64)batch * (dl * rows + 2 * rows + 2 * nlimbs + c->alpha + cl) * c->n * sizeof(u64);
+namespace {
+
+// One key-switch call as its three steps see it: the plan (ks_plan.hpp: paths, sizes, regions),
+// the workspace the regions lie in and the caller's operands.
+struct KsRun {
+  const fhe_ctx* c;
+  const KsPlan& p;
+  u64* ws;
+  const CAll& call;
+  const u64 *d2_own, *evk_b, *evk_a;
+  u64 *ks0, *ks1;
+  const KsEpilogue& ep;  // out_bs resolved
+  const KsHoist* hoist;
+  hipStream_t s;
+  int modup() const;
+  int inner() const;
+  int moddown() const;
+};
+
+// ModUp + NTT, per digit, for every row outside the digit itself: the NTT-form (fused: the
+// column-passed) extended rows of every live digit land in the ext region.
+int KsRun::modup() const {
+  const u32 L = c->L, K = c->K, M = L + K, alpha = c->alpha, Lq = p.liveq;
+  const u32 limb0 = p.limb0, nlimbs = p.nlimbs, rows = p.rows, batch = p.batch;
+  const u64 n = c->n, rn = (u64)rows * n, B = batch;
+  u64* yws = ws + p.yws;  // [B][alpha][N]
+  const RowMap map{nlimbs, limb0, L};
+  // digit j's slice of a [dnum][alpha](x [L + K]) table: the level's own for a partial last digit
+  auto dig = [&](const ulonglong2* top, const ulonglong2* lvl, u32 j, size_t per) {
+    return p.partial && j == p.digits - 1 ? lvl + (size_t)p.level * per : top + (size_t)j * per;
+  };
+  auto ntt_fwd = [&](u64* e, u32 l0, u32 nl) {
+    return p.fused ? launch_ntt_col_fwd(c, e, rn, e, rn, batch, l0, nl, s)
+                   : launch_ntt(c, true, e, e, batch, rn, l0, nl, s);
+  };
+  int rc;
+  // Prepared inputs (no per-digit scaling pass into the shared yws) put every digit's conversion
+  // pass in one launch.
+  ModUpColArgs pend[4];
+  u32 npend = 0;
+  for (u32 j = 0; j < p.digits; ++j) {
+    const u32 lo = p.lo(j), hi = p.hi(j);
+    u64* e = ws + p.ext + (u64)j * B * rn;
+    KOff ko{};  // the digit's source rows in c_all
+    for (u32 k = 0; k < hi - lo; ++k) ko.o[k] = call.off(lo + k, n);
+    if (p.fused_up) {
+      const u32 S = hi - lo;
+      // the conversion's inputs y_k = [x_k (D^_k)^-1]: already in c_all when it is prepared (its
+      // INTT folded the factor in), else one scaling pass into yws
+      const u64* ysrc = call.ptr;
+      u64 ybs = call.bs, yoff[4] = {};
+      for (u32 k = 0; k < S; ++k) yoff[k] = ko.o[k];
+      if (!call.scaled) {
+        k_modup_scale<<<dim3((u32)(n / kThreads), S, batch), kThreads, 0, s>>>(
+            call.ptr, call.bs, ko, lo, yws, S, c->log_n,
+            dig(c->d_modup_inv, c->d_lvl_inv, j, alpha), c->d_mods, p.split30);
+        FHE_HIP_CHECK(hipGetLastError());
+        ysrc = yws;
+        ybs = (u64)S * n;
+        for (u32 k = 0; k < S; ++k) yoff[k] = (u64)k * n;
+      }
+      // this rank's own rows of digit j are skipped: ks_row_inner takes them from d2_own
+      const u32 own_lo = std::max(lo, limb0), own_hi = std::min(hi, limb0 + nlimbs);
+      const u32 skip_len = own_hi > own_lo ? own_hi - own_lo : 0;
+      const u32 skip_at = skip_len ? own_lo - limb0 : rows;
+      const ModUpColArgs ma{ysrc, ybs, {yoff[0], yoff[1], yoff[2], yoff[3]}, e, rn, S,
+                            rows - skip_len, skip_at, skip_len, nlimbs, limb0, L, batch,
+                            p.pscale     ? dig(c->d_modup_hat_rwp, c->d_lvl_hat_rwp, j, alpha * M)
+                            : p.mont_ext ? dig(c->d_modup_hat_rw, c->d_lvl_hat_rw, j, alpha * M)
+                                         : dig(c->d_modup_hat_w, c->d_lvl_hat_w, j, alpha * M),
+                            M};
+      if (call.scaled && npend < 4) {
+        pend[npend++] = ma;
+        continue;
+      }
+      if ((rc = launch_modup_col(c, ma, s))) return rc;
+      continue;
+    }
+    const BcArgs up{call.ptr, call.bs, ko, lo, e, rn, rows, map, lo, hi, batch};
+    if ((rc = baseconv_any(hi - lo, up, n, dig(c->d_modup_inv, c->d_lvl_inv, j, alpha),
+                           dig(c->d_modup_hat, c->d_lvl_hat, j, alpha * M), M, c->d_mods, c->wide,
+                           s)))
+      return rc;
+    // own Q-limbs outside [lo, hi): up to two ranges, then the P-limbs
+    const u32 a0 = limb0, a1 = std::min(limb0 + nlimbs, lo);
+    if (a1 > a0 && (rc = ntt_fwd(e, a0, a1 - a0))) return rc;
+    const u32 b0 = std::max(limb0, hi), b1 = limb0 + nlimbs;
+    if (b1 > b0 && (rc = ntt_fwd(e + (u64)(b0 - limb0) * n, b0, b1 - b0))) return rc;
+    if ((rc = ntt_fwd(e + (u64)nlimbs * n, L, K))) return rc;
+  }
+  if (npend && (rc = launch_modup_cols(c, pend, npend, s))) return rc;
+  if (p.hoist_up) {
+    // the row-forward passes of every live digit's extended rows: [0, lo) and [hi, rows), whose
+    // limbs are [0, lo) and (the live Q-limbs past the digit, then P) [hi, Lq) u [L, L + K) in the
+    // single-device form (limb0 = 0, nlimbs = Lq); at the top level the two ranges are one run
+    // [hi, L + K), below it the special rows' limb is L + (r - Lq) and they take a launch of their
+    // own
+    for (u32 j = 0; j < p.digits; ++j) {
+      const u32 lo = p.lo(j), hi = p.hi(j);
+      u64* e = ws + p.ext + (u64)j * B * rn;
+      if (limb0 != 0 || nlimbs != Lq) {
+        set_error("keyswitch: the hoisted ModUp is single-device (all live Q-limbs)");
+        return kInvalid;
+      }
+      if ((rc = launch_ntt_row_fwd_r2(c, e, rn, e, rn, batch, 0, lo, s))) return rc;
+      if (Lq == L) {
+        if ((rc = launch_ntt_row_fwd_r2(c, e + (u64)hi * n, rn, e + (u64)hi * n, rn, batch, hi,
+                                        rows - hi, s)))
+          return rc;
+        continue;
+      }
+      if ((rc = launch_ntt_row_fwd_r2(c, e + (u64)hi * n, rn, e + (u64)hi * n, rn, batch, hi,
+                                      Lq - hi, s)) ||
+          (rc = launch_ntt_row_fwd_r2(c, e + (u64)Lq * n, rn, e + (u64)Lq * n, rn, batch, L, K, s)))
+        return rc;
+    }
+  }
+  prof_mark(s, "ks_modup");
+  return kOk;
 }
 
-int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const u64* c_all,
-                           const u64* d2_own, const u64* evk_b, const u64* evk_a, u32 limb0,
-                           u32 nlimbs, u32 batch, void* ws, hipStream_t s) {
-  return launch_keyswitch_shard(c, ks0, ks1, CAll::contiguous(c_all, c->L, c->n), d2_own, evk_b,
-                                evk_a, limb0, nlimbs, batch, ws, s);
+// The inner product of the digits with the key into the accumulators: k_ks_row_inner (fused: with
+// the digits' row-forward pass; qfin: the special rows only) or k_ks_inner; nothing where the
+// caller has filled the accumulators.
+int KsRun::inner() const {
+  const u32 L = c->L, K = c->K, alpha = c->alpha, rows = p.rows, nlimbs = p.nlimbs;
+  const u32 batch = p.batch, key_rows = p.key_rows;
+  const u64 n = c->n, acc_ws = p.acc_stride();
+  u64* ext = ws + p.ext;
+  u64* acc = ws + p.acc;
+  if (p.fused) {
+    KsRowArgs ka{acc, acc_ws, ext, acc_ws, d2_own, evk_b, evk_a, rows, nlimbs, p.limb0, L,
+                 alpha, L, batch, p.mont_ext};
+    ka.dnum = p.digits;
+    ka.key_rows = key_rows;
+    ka.pinv = p.row_pinv ? 1u : 0u;
+    ka.rscale = p.pscale ? c->d_rpinv : nullptr;
+    if (p.qfin) {
+      ka.row0 = nlimbs;
+      ka.nrows = K;
+    }
+    if (int rc = launch_ks_row_inner(c, ka, s)) return rc;
+  }
+  const RowMap map{nlimbs, p.limb0, L};
+  const u32 gal = hoist ? hoist->galois : 0;
+  const dim3 gi((u32)(n / kThreads), rows);
+  if (!p.fused && p.mode != kKsAccReady) switch (p.digits) {
+#define X(k)                                                                                     \
+  case k:                                                                                        \
+    k_ks_inner<k><<<gi, kThreads, 0, s>>>(acc, acc_ws, ext, d2_own, evk_b, evk_a, rows,   \
+                                          nlimbs, map, alpha, L, batch, c->log_n, c->d_mods,    \
+                                          gal, (u64)key_rows * n, key_rows - K);                \
+    break;
+    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+#undef X
+  }
+  FHE_HIP_CHECK(hipGetLastError());
+  prof_mark(s, "ks_inner");
+  return kOk;
 }
+
+// ModDown: INTT the P rows of both accumulators, convert P -> own Q-limbs, NTT, finish
+int KsRun::moddown() const {
+  const u32 L = c->L, K = c->K, M = L + K, rows = p.rows, nlimbs = p.nlimbs, limb0 = p.limb0;
+  const u32 batch = p.batch;
+  const u64 n = c->n, rn = (u64)rows * n, acc_ws = p.acc_stride();
+  u64* ext = ws + p.ext;
+  u64* acc = ws + p.acc;
+  u64* conv = ws + p.conv;  // [2][B][nlimbs][N]
+  u64* accp = acc + (u64)nlimbs * n;
+  int rc;
+  // Fused ModDown: the P -> Q conversion runs inside the column-forward pass of the conversion NTT
+  // (k_modup_col, as ModUp), on the P rows the INTT has already scaled into the ext region (free
+  // once the inner product has run): conv is never written in coefficient form.
+  if (p.fused_down) {
+    // the INTT writes y = [x_k (P^_k)^-1]_{p_k} straight into [2 batch][K][N] (its last stage
+    // folds N^-1 (P^_k)^-1, c->d_nfold_down): no separate scaling pass
+    u64* ydn = p.qfin ? accp : hoist ? hoist->ydn : ext;
+    const u64 yps = p.qfin ? rn : (u64)K * n;  // poly stride of the scaled P rows
+    if ((rc = p.row_pinv ? launch_ntt_col_inv(c, accp, rn, ydn, yps, 2 * batch, L, K, s,
+                                              c->d_nfold_down, p.split30)
+                         : launch_ntt_strided(c, false, accp, rn, ydn, yps, 2 * batch, L, K, s,
+                                              c->d_nfold_down, p.split30)))
+      return rc;
+    prof_mark(s, "ks_moddown_conv");
+    const ModUpColArgs md{ydn, yps, {0, n, 2 * n, 3 * n}, conv, (u64)nlimbs * n, K, nlimbs,
+                          nlimbs, 0, nlimbs, limb0, 0, 2 * batch,
+                          p.pscale ? c->d_moddown_hat_wp : c->d_moddown_hat_w, M};
+    if ((rc = launch_modup_col(c, md, s))) return rc;
+    prof_mark(s, "ks_moddown_col");
+    if (p.qfin) {  // (outputs are d2_own itself or disjoint from it: ks_check_alias)
+      const KsFinArgs fa{ext, acc_ws, d2_own, evk_b, evk_a, rows, nlimbs, limb0, c->alpha, L,
+                         batch, c->d_rpinv, conv, ks0, ks1, ep, p.digits, p.key_rows};
+      if ((rc = launch_ks_row_fin(c, fa, s))) return rc;
+      prof_mark(s, "ks_row_fin");
+      return kOk;
+    }
+  } else {
+    if ((rc = launch_ntt(c, false, accp, accp, 2 * batch, rn, L, K, s))) return rc;
+    const BcArgs down{accp, rn, rows_contiguous(K, n), L, conv, (u64)nlimbs * n, nlimbs,
+                      RowMap{nlimbs, limb0, 0}, 0, 0, 2 * batch};
+    if ((rc = baseconv_any(K, down, n, c->d_moddown_inv, c->d_moddown_hat, M, c->d_mods, c->wide,
+                           s)))
+      return rc;
+    prof_mark(s, "ks_moddown_conv");
+    if (!p.fused) {
+      if ((rc = launch_ntt(c, true, conv, conv, 2 * batch, (u64)nlimbs * n, limb0, nlimbs, s)))
+        return rc;
+      k_moddown_finish<<<dim3((u32)(n / kThreads), nlimbs, batch), kThreads, 0, s>>>(
+          ks0, ks1, acc, acc_ws, rows, conv, nlimbs, limb0, c->log_n, c->d_pinv, c->d_mods,
+          ep);
+      FHE_HIP_CHECK(hipGetLastError());
+      prof_mark(s, "moddown_finish");
+      return kOk;
+    }
+    if ((rc = launch_ntt_col_fwd(c, conv, (u64)nlimbs * n, conv, (u64)nlimbs * n, 2 * batch, limb0,
+                                 nlimbs, s)))
+      return rc;
+    prof_mark(s, "ks_moddown_col");
+  }
+  // conv is column-passed either way: the conversion NTT's row pass finishes ModDown in its
+  // epilogue (k_moddown_row)
+  const ModDownRowArgs da{conv, ks0, ks1, acc, acc_ws, rows, nlimbs, limb0, batch, ep};
+  if ((rc = launch_moddown_row(c, da, s))) return rc;
+  prof_mark(s, "moddown_row_finish");
+  return kOk;
+}
+
+}  // namespace
 
 int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& call,
                            const u64* d2_own, const u64* evk_b, const u64* evk_a, u32 limb0,
@@ -482,248 +696,30 @@ int launch_keyswitch_shard(const fhe_ctx* c, u64* ks0, u64* ks1, const CAll& cal
                                 (u64)(batch - 1) * ep.out_bs + nw, ep.out_bs == nw, "keyswitch"))
       return rc;
   }
-  const u32 L = c->L, K = c->K, M = L + K, alpha = c->alpha, rows = nlimbs + K;
-  // The chain's live Q-limbs and digits: all L and dnum, or a level call's first `level` limbs in
-  // ceil(level / alpha) digits of the same width, the last one partial where alpha does not divide
-  // level (its constants: the d_lvl_* tables).  The key is the top-level one either way; a level
-  // call reads rows {0 .. level-1} u {L .. L+K-1} of its digits j < dl in place (key_rows).
-  const u32 Lq = level ? level : L, dl = level ? ks_level_digits(c, level) : c->dnum;
-  const u32 key_rows = level ? M : rows;
-  const bool part = level && ks_level_partial(c, level);
-  // digit j's slice of a [dnum][alpha](x [L + K]) table: the level's own for a partial last digit
-  auto dig = [&](const ulonglong2* top, const ulonglong2* lvl, u32 j, size_t per) {
-    return part && j == dl - 1 ? lvl + (size_t)level * per : top + (size_t)j * per;
-  };
-  const u64 n = c->n, rn = (u64)rows * n, B = batch;
-  u64* ext = static_cast<u64*>(ws);          // [dl][B][rows][N]
-  u64* acc = ext + (u64)dl * B * rn;         // [2][B][rows][N]
-  u64* conv = acc + 2 * B * rn;              // [2][B][nlimbs][N]
-  const u64 acc_ws = B * rn;
-  const RowMap map{nlimbs, limb0, L};
-  int rc;
-  // Fused path: for dnum <= 4 the digits get only their column-forward pass here, and one fused
-  // kernel (ntt.hip, k_ks_row_inner) runs every digit's row-forward pass and the inner product
-  // (no NTT-form ext in HBM, no separate inner-product pass); otherwise full NTTs + k_ks_inner.
-  // Wide contexts (a modulus >= 2^61) take the unfused kernels: the fused ones rely on lazy
-  // ranges and 128-bit sums that need q < 2^61.
-  // Hoisted rotations (KsHoist) take the unfused kernels: the digits must exist in NTT form in
-  // HBM so that each rotation's inner product can gather them through its automorphism.
-  const bool fused = !hoist && ks_fused(c);
-  const u32 gal = hoist ? hoist->galois : 0;
-  // The hoisted ModUp (modup_only) on the contexts the fused ModUp serves: the same conversion
-  // column pass (plain table: the gathered inner products read plain residues), then one
-  // row-forward pass per digit range (launch_ntt_row_fwd_r2), so the NTT-form digits land in HBM
-  // for the gathers; in place of k_baseconv + a full NTT per range.
-  const bool hoist_up = hoist && hoist->modup_only && ks_prepared(c);
-  // Fused ModUp (with the fused row kernel, digits of <= 4 limbs): the base conversion runs
-  // inside the column-forward pass (ntt.hip k_modup_col) after a one-pass prologue that scales the
-  // digit's source rows; the extended rows are never written in coefficient form.
-  const bool fused_up = (fused && alpha <= 4) || hoist_up;
-  // lz16 fused ModUp: the extended rows come out times R = 2^64 (d_modup_hat_rw / _rwp), which the fused
-  // row kernel's Montgomery inner product cancels (KsRowArgs::mont)
-  const bool mont_ext = fused_up && !hoist_up && c->lz16;
-  if (call.scaled && !fused_up && (!hoist || hoist->modup_only)) {
+  const KsPlan p = ks_plan(ks_shape(c), limb0, nlimbs, batch, level,
+                           hoist ? hoist->mode() : kKsFull, hoist && hoist->ydn);
+  // (a hoisted rotation's inner step and a ModDown of ready accumulators skip ModUp)
+  const bool modup = p.mode == kKsFull || p.mode == kKsModUpOnly;
+  if (call.scaled && !p.fused_up && modup) {
     set_error("keyswitch: a prepared (pre-scaled) input needs the fused ModUp (ks_prepared)");
     return kInvalid;
   }
-  // ModDown's finish: k_moddown_row after the fused conversion (fused_down; a hoisted rotation's
-  // inner step too, with its own scratch for the INTT output) or after k_baseconv (fused), else
-  // the unfused k_moddown_finish
-  const bool fused_down = K <= 4 && ((fused && (u64)dl * rows >= 2 * (u64)K) ||
-                                     (hoist && hoist->ydn && ks_hoist_fused_down(c)));
-  // ModDown's P^-1 folded into the accumulators' Q rows (the ModUp conversion tables of the Q
-  // targets and the own digit's R factor carry P^-1) and into the P -> Q conversion table, so
-  // k_moddown_row's finish is a subtraction: the lz16 fused ModUp with the fused ModDown
-  const bool pscale = mont_ext && fused_down;
   // k_moddown_finish adds its addend rows un-permuted: a sigma-gathered addend
-  // (KsEpilogue::add_gal, which only k_moddown_row implements) reaching it would give a wrong
-  // ciphertext with no error, so a caller whose path predicate (ks_fused / ks_hoist_fused_down)
-  // drifts from this selection is refused before anything is launched
-  if (ep.add_gal && !fused_down && !fused) {
+  // (KsEpilogue::add_gal, which only the row finishes implement) reaching it would give a wrong
+  // ciphertext with no error.  Callers take the choice from the same plan (KsPlan::row_finish);
+  // one that does not is refused before anything is launched.
+  if (ep.add_gal && !p.row_finish) {
     set_error("keyswitch: a sigma-gathered epilogue addend needs a k_moddown_row finish");
     return kInvalid;
   }
-  if (!hoist || hoist->modup_only) {  // ModUp (a hoisted rotation's inner step skips it)
-  u64* yws = conv + 2 * B * (u64)nlimbs * n;  // [B][alpha][N]
-  auto ntt_fwd = [&](u64* p, u32 l0, u32 nl) {
-    return fused ? launch_ntt_col_fwd(c, p, rn, p, rn, batch, l0, nl, s)
-                 : launch_ntt(c, true, p, p, batch, rn, l0, nl, s);
-  };
-  // ModUp + NTT, per digit, for every row outside the digit itself.  Prepared inputs (no
-  // per-digit scaling pass into the shared yws) put every digit's conversion pass in one launch.
-  ModUpColArgs pend[4];
-  u32 npend = 0;
-  for (u32 j = 0; j < dl; ++j) {
-    const u32 lo = j * alpha, hi = std::min(Lq, lo + alpha);
-    u64* e = ext + (u64)j * B * rn;
-    KOff ko{};  // the digit's source rows in c_all
-    for (u32 k = 0; k < hi - lo; ++k) ko.o[k] = call.off(lo + k, n);
-    if (fused_up) {
-      const u32 S = hi - lo;
-      // the conversion's inputs y_k = [x_k (D^_k)^-1]: already in c_all when it is prepared (its
-      // INTT folded the factor in), else one scaling pass into yws
-      const u64* ysrc = call.ptr;
-      u64 ybs = call.bs, yoff[4] = {};
-      for (u32 k = 0; k < S; ++k) yoff[k] = ko.o[k];
-      if (!call.scaled) {
-        k_modup_scale<<<dim3((u32)(n / kThreads), S, batch), kThreads, 0, s>>>(
-            call.ptr, call.bs, ko, lo, yws, S, c->log_n,
-            dig(c->d_modup_inv, c->d_lvl_inv, j, alpha), c->d_mods, ks_split30(c));
-        FHE_HIP_CHECK(hipGetLastError());
-        ysrc = yws;
-        ybs = (u64)S * n;
-        for (u32 k = 0; k < S; ++k) yoff[k] = (u64)k * n;
-      }
-      // this rank's own rows of digit j are skipped: ks_row_inner takes them from d2_own
-      const u32 own_lo = std::max(lo, limb0), own_hi = std::min(hi, limb0 + nlimbs);
-      const u32 skip_len = own_hi > own_lo ? own_hi - own_lo : 0;
-      const u32 skip_at = skip_len ? own_lo - limb0 : rows;
-      const ModUpColArgs ma{ysrc, ybs, {yoff[0], yoff[1], yoff[2], yoff[3]}, e, rn, S,
-                            rows - skip_len, skip_at, skip_len, nlimbs, limb0, L, batch,
-                            pscale     ? dig(c->d_modup_hat_rwp, c->d_lvl_hat_rwp, j, alpha * M)
-                            : mont_ext ? dig(c->d_modup_hat_rw, c->d_lvl_hat_rw, j, alpha * M)
-                                       : dig(c->d_modup_hat_w, c->d_lvl_hat_w, j, alpha * M),
-                            M};
-      if (call.scaled && npend < 4) {
-        pend[npend++] = ma;
-        continue;
-      }
-      if ((rc = launch_modup_col(c, ma, s))) return rc;
-      continue;
-    }
-    const BcArgs up{call.ptr, call.bs, ko, lo, e, rn, rows, map, lo, hi, batch};
-    if ((rc = baseconv_any(hi - lo, up, n, dig(c->d_modup_inv, c->d_lvl_inv, j, alpha),
-                           dig(c->d_modup_hat, c->d_lvl_hat, j, alpha * M), M, c->d_mods, c->wide,
-                           s)))
-      return rc;
-    // own Q-limbs outside [lo, hi): up to two ranges, then the P-limbs
-    const u32 a0 = limb0, a1 = std::min(limb0 + nlimbs, lo);
-    if (a1 > a0 && (rc = ntt_fwd(e, a0, a1 - a0))) return rc;
-    const u32 b0 = std::max(limb0, hi), b1 = limb0 + nlimbs;
-    if (b1 > b0 && (rc = ntt_fwd(e + (u64)(b0 - limb0) * n, b0, b1 - b0))) return rc;
-    if ((rc = ntt_fwd(e + (u64)nlimbs * n, L, K))) return rc;
+  const KsRun r{c, p, static_cast<u64*>(ws), call, d2_own, evk_b, evk_a, ks0, ks1, ep, hoist, s};
+  // (the shared ModUp of hoisted rotations ends there, its NTT-form digits left in the ext region)
+  if (modup) {
+    if (int rc = r.modup()) return rc;
+    if (p.mode == kKsModUpOnly) return kOk;
   }
-  if (npend && (rc = launch_modup_cols(c, pend, npend, s))) return rc;
-  if (hoist_up) {
-    // the row-forward passes of every live digit's extended rows: [0, lo) and [hi, rows), whose
-    // limbs are [0, lo) and (the live Q-limbs past the digit, then P) [hi, Lq) u [L, L + K) in the
-    // single-device form (limb0 = 0, nlimbs = Lq); at the top level the two ranges are one run
-    // [hi, L + K), below it the special rows' limb is L + (r - Lq) and they take a launch of their
-    // own
-    for (u32 j = 0; j < dl; ++j) {
-      const u32 lo = j * alpha, hi = std::min(Lq, lo + alpha);
-      u64* e = ext + (u64)j * B * rn;
-      if (limb0 != 0 || nlimbs != Lq) {
-        set_error("keyswitch: the hoisted ModUp is single-device (all live Q-limbs)");
-        return kInvalid;
-      }
-      if ((rc = launch_ntt_row_fwd_r2(c, e, rn, e, rn, batch, 0, lo, s))) return rc;
-      if (Lq == L) {
-        if ((rc = launch_ntt_row_fwd_r2(c, e + (u64)hi * n, rn, e + (u64)hi * n, rn, batch, hi,
-                                        rows - hi, s)))
-          return rc;
-        continue;
-      }
-      if ((rc = launch_ntt_row_fwd_r2(c, e + (u64)hi * n, rn, e + (u64)hi * n, rn, batch, hi,
-                                      Lq - hi, s)) ||
-          (rc = launch_ntt_row_fwd_r2(c, e + (u64)Lq * n, rn, e + (u64)Lq * n, rn, batch, L, K, s)))
-        return rc;
-    }
-  }
-  prof_mark(s, "ks_modup");
-  if (hoist) return kOk;  // modup_only: the NTT-form digits stay in the workspace's ext region
-  }
-  // the fused row kernel also runs the first (row) pass of ModDown's INTT on the special rows
-  const bool row_pinv = fused && fused_down;
-  // With P^-1 in the constants the Q rows wait for ModDown's conversion and finish in the same
-  // workgroup (k_ks_row_fin): the row kernel covers only the special rows first, their column
-  // inverse runs in place in the accumulators (the ext region stays intact for the Q rows), and
-  // neither the accumulators' Q rows nor k_moddown_row's pass over them touch HBM.
-  // (outputs are d2_own itself or disjoint from it: ks_check_alias above)
-  const bool qfin = pscale && row_pinv;
-  if (fused) {
-    KsRowArgs ka{acc, acc_ws, ext, B * rn, d2_own, evk_b, evk_a, rows, nlimbs, limb0, L,
-                 alpha, L, batch, mont_ext};
-    ka.dnum = dl;
-    ka.key_rows = key_rows;
-    ka.pinv = row_pinv ? 1u : 0u;
-    ka.rscale = pscale ? c->d_rpinv : nullptr;
-    if (qfin) {
-      ka.row0 = nlimbs;
-      ka.nrows = K;
-    }
-    if ((rc = launch_ks_row_inner(c, ka, s))) return rc;
-  }
-  const dim3 gi((u32)(n / kThreads), rows);
-  if (!fused && !(hoist && hoist->acc_ready)) switch (dl) {
-#define X(k)                                                                                     \
-  case k:                                                                                        \
-    k_ks_inner<k><<<gi, kThreads, 0, s>>>(acc, acc_ws, ext, d2_own, evk_b, evk_a, rows, nlimbs, \
-                                          map, alpha, L, batch, c->log_n, c->d_mods, gal,       \
-                                          (u64)key_rows * n, key_rows - K);                     \
-    break;
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
-#undef X
-  }
-  FHE_HIP_CHECK(hipGetLastError());
-  prof_mark(s, "ks_inner");
-  // ModDown: INTT the P rows of both accumulators, convert P -> own Q-limbs, NTT, finish
-  u64* accp = acc + (u64)nlimbs * n;
-  // Fused ModDown (fused path, K <= 4): the P -> Q conversion runs inside the column-forward
-  // pass of the conversion NTT (k_modup_col, as ModUp), on the P rows the INTT has already scaled
-  // into the ext region (free once the inner product has run): conv is never written in
-  // coefficient form.
-  if (fused_down) {
-    // the INTT writes y = [x_k (P^_k)^-1]_{p_k} straight into [2 batch][K][N] (its last stage
-    // folds N^-1 (P^_k)^-1, c->d_nfold_down): no separate scaling pass
-    u64* ydn = qfin ? accp : hoist ? hoist->ydn : ext;
-    const u64 yps = qfin ? rn : (u64)K * n;  // poly stride of the scaled P rows
-    if ((rc = row_pinv ? launch_ntt_col_inv(c, accp, rn, ydn, yps, 2 * batch, L, K, s,
-                                            c->d_nfold_down, ks_split30(c))
-                       : launch_ntt_strided(c, false, accp, rn, ydn, yps, 2 * batch, L, K,
-                                            s, c->d_nfold_down, ks_split30(c))))
-      return rc;
-    prof_mark(s, "ks_moddown_conv");
-    const ModUpColArgs md{ydn, yps, {0, n, 2 * n, 3 * n}, conv, (u64)nlimbs * n, K, nlimbs,
-                          nlimbs, 0, nlimbs, limb0, 0, 2 * batch,
-                          pscale ? c->d_moddown_hat_wp : c->d_moddown_hat_w, M};
-    if ((rc = launch_modup_col(c, md, s))) return rc;
-    prof_mark(s, "ks_moddown_col");
-    if (qfin) {
-      const KsFinArgs fa{ext, B * rn, d2_own, evk_b, evk_a, rows, nlimbs, limb0, alpha, L, batch,
-                         c->d_rpinv, conv, ks0, ks1, ep, dl, key_rows};
-      if ((rc = launch_ks_row_fin(c, fa, s))) return rc;
-      prof_mark(s, "ks_row_fin");
-      return kOk;
-    }
-    const ModDownRowArgs da{conv, ks0, ks1, acc, acc_ws, rows, nlimbs, limb0, batch, ep};
-    if ((rc = launch_moddown_row(c, da, s))) return rc;
-    prof_mark(s, "moddown_row_finish");
-    return kOk;
-  }
-  if ((rc = launch_ntt(c, false, accp, accp, 2 * batch, rn, L, K, s))) return rc;
-  const BcArgs down{accp, rn, rows_contiguous(K, n), L, conv, (u64)nlimbs * n, nlimbs,
-                    RowMap{nlimbs, limb0, 0}, 0, 0, 2 * batch};
-  if ((rc = baseconv_any(K, down, n, c->d_moddown_inv, c->d_moddown_hat, M, c->d_mods, c->wide, s)))
-    return rc;
-  prof_mark(s, "ks_moddown_conv");
-  if (fused) {  // conversion NTT's row pass finishes ModDown in its epilogue
-    if ((rc = launch_ntt_col_fwd(c, conv, (u64)nlimbs * n, conv, (u64)nlimbs * n, 2 * batch, limb0,
-                                 nlimbs, s)))
-      return rc;
-    prof_mark(s, "ks_moddown_col");
-    const ModDownRowArgs da{conv, ks0, ks1, acc, acc_ws, rows, nlimbs, limb0, batch, ep};
-    if ((rc = launch_moddown_row(c, da, s))) return rc;
-    prof_mark(s, "moddown_row_finish");
-    return kOk;
-  }
-  if ((rc = launch_ntt(c, true, conv, conv, 2 * batch, (u64)nlimbs * n, limb0, nlimbs, s)))
-    return rc;
-  k_moddown_finish<<<dim3((u32)(n / kThreads), nlimbs, batch), kThreads, 0, s>>>(
-      ks0, ks1, acc, acc_ws, rows, conv, nlimbs, limb0, c->log_n, c->d_pinv, c->d_mods, ep);
-  FHE_HIP_CHECK(hipGetLastError());
-  prof_mark(s, "moddown_finish");
-  return kOk;
+  if (int rc = r.inner()) return rc;
+  return r.moddown();
 }
 
 int launch_baseconv(const fhe_ctx* c, u64* out, const u64* in, u32 s0, u32 S, u32 t0, u32 T,

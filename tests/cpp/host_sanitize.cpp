@@ -1,6 +1,6 @@
 // Host-code sanitizer run (ASan/UBSan on the host side): the pure-host parts of
 // libfhecore -- number theory and table construction (csrc/host_tables.cpp), the FHEC wire
-// parser (csrc/wire.cpp) -- and the C oracle (oracle/fhe_oracle.c, test infrastructure), built
+// parser (csrc/wire.cpp), the key-switch plan (csrc/ks_plan.hpp) -- and the C oracle (oracle/fhe_oracle.c, test infrastructure), built
 // with -fsanitize=address,undefined by tests/cpp/Makefile and exercised here with checks of their
 // own.  GPU code is out of scope (no device sanitizers on this pool).  tests/test_sanitizers.py
 // builds and runs it; it prints "host_sanitize OK" and exits 0 when every check holds.
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../gpu-fhe_amd/csrc/host_tables.hpp"
+#include "../../gpu-fhe_amd/csrc/ks_plan.hpp"
 #include "../../gpu-fhe_amd/csrc/wire.hpp"
 
 extern "C" {
@@ -258,7 +259,112 @@ static void test_oracle() {
   for (u64 i = 0; i < Lq * n; ++i) CHECK(k0[i] < qs[i / n] && k1[i] < qs[i / n]);
 }
 
+// The key-switch plan (csrc/ks_plan.hpp) against the expressions launch_keyswitch_shard and its
+// callers computed inline before the plan existed, restated here once: the path flags, and the
+// workspace size batch (dl rows + 2 rows + 2 nlimbs + alpha + cl) n 8.  The one deliberate
+// difference: the live digits are ceil(liveQ / alpha) in every mode (the old level-0 form took
+// dnum, which counts an empty last digit), so the size formula is compared on the contexts
+// without one.
+struct KsRef {
+  bool fused, hoist_up, fused_up, mont_ext, fused_down, pscale, row_pinv, qfin, part, prepared,
+      split30;
+};
+static KsRef ks_ref(const KsShape& c, u32 nlimbs, u32 level, KsMode mode, bool ydn) {
+  const bool hoist = mode != kKsFull, modup_only = mode == kKsModUpOnly;
+  const u32 liveq = level ? level : c.L, dl = (liveq + c.alpha - 1) / c.alpha;
+  const u32 rows = nlimbs + c.K;
+  const bool ks_fused = c.dnum <= 4 && !c.wide;
+  const bool ks_hoist_fused_down = c.K <= 4 && c.dnum <= 4 && !c.wide;
+  KsRef r;
+  r.prepared = c.K > 0 && c.dnum <= 4 && c.alpha <= 4 && !c.wide;
+  r.split30 = !c.lz16;
+  r.part = level && level < c.L && level % c.alpha != 0;
+  r.fused = !hoist && ks_fused;
+  r.hoist_up = hoist && modup_only && r.prepared;
+  r.fused_up = (r.fused && c.alpha <= 4) || r.hoist_up;
+  r.mont_ext = r.fused_up && !r.hoist_up && c.lz16;
+  r.fused_down = c.K <= 4 && ((r.fused && (u64)dl * rows >= 2 * (u64)c.K) ||
+                              (hoist && ydn && ks_hoist_fused_down));
+  r.pscale = r.mont_ext && r.fused_down;
+  r.row_pinv = r.fused && r.fused_down;
+  r.qfin = r.pscale && r.row_pinv;
+  return r;
+}
+
+static void check_ks_plan(const KsShape& c, u32 limb0, u32 nlimbs, u32 batch, u32 level,
+                          KsMode mode, bool ydn) {
+  const KsPlan p = ks_plan(c, limb0, nlimbs, batch, level, mode, ydn);
+  const KsRef r = ks_ref(c, nlimbs, level, mode, ydn);
+  const u32 liveq = level ? level : c.L;
+  CHECK(p.limb0 == limb0 && p.nlimbs == nlimbs && p.batch == batch && p.level == level &&
+        p.mode == mode);
+  CHECK(p.liveq == liveq && p.digits == (liveq + c.alpha - 1) / c.alpha);
+  CHECK(p.rows == nlimbs + c.K && p.key_rows == (level ? c.L + c.K : nlimbs + c.K));
+  CHECK(p.partial == r.part);
+  CHECK(p.fused == r.fused && p.hoist_up == r.hoist_up && p.fused_up == r.fused_up &&
+        p.mont_ext == r.mont_ext && p.fused_down == r.fused_down && p.pscale == r.pscale &&
+        p.row_pinv == r.row_pinv && p.qfin == r.qfin && p.prepared == r.prepared &&
+        p.split30 == r.split30);
+  // the guard's condition: a sigma-gathered addend was refused when !fused_down && !fused
+  CHECK(p.row_finish == (r.fused_down || r.fused));
+  // the size, where no digit is empty (dl = dnum at level 0, ceil(level / alpha) below)
+  if (c.dnum == (c.L + c.alpha - 1) / c.alpha) {
+    const u64 dl = level ? (level + c.alpha - 1) / c.alpha : c.dnum, cl = level ? level : c.L;
+    const u64 rows = nlimbs + c.K;
+    CHECK(p.bytes() == (u64)batch * (dl * rows + 2 * rows + 2 * nlimbs + c.alpha + cl) * c.n * 8);
+  }
+  // regions in order, each as large as its contents, the last one ending at the total
+  const u64 bn = (u64)batch * c.n;
+  CHECK(p.ext == 0 && p.acc - p.ext == p.digits * bn * p.rows && p.acc >= p.ext);
+  CHECK(p.conv >= p.acc && p.conv - p.acc == 2 * bn * p.rows);
+  CHECK(p.yws >= p.conv && p.yws - p.conv == 2 * bn * nlimbs);
+  CHECK(p.call >= p.yws && p.call - p.yws == bn * c.alpha);
+  CHECK(p.total >= p.call && p.total - p.call == bn * liveq);
+  CHECK(p.ext_words() == p.digits * bn * p.rows && p.acc_stride() == bn * p.rows);
+  // the digits tile the live limbs: never empty, never wider than alpha, never past liveq
+  CHECK(p.digits >= 1 && p.lo(0) == 0 && p.hi(p.digits - 1) == liveq);
+  for (u32 j = 0; j < p.digits; ++j) {
+    CHECK(p.lo(j) < p.hi(j) && p.hi(j) <= liveq && p.hi(j) - p.lo(j) <= c.alpha);
+    if (j + 1 < p.digits) CHECK(p.hi(j) == p.lo(j + 1));
+  }
+  CHECK(!p.pscale || (p.mont_ext && p.fused_down));
+  CHECK(!p.qfin || (p.pscale && p.row_pinv));
+  CHECK(!p.mont_ext || (c.lz16 && p.fused_up));
+  CHECK(!p.fused_up || c.alpha <= 4);
+  CHECK(!p.fused_down || c.K <= 4);
+  if (c.wide)
+    CHECK(!p.fused && !p.hoist_up && !p.fused_up && !p.mont_ext && !p.fused_down && !p.pscale &&
+          !p.row_pinv && !p.qfin);
+  if (mode != kKsFull) CHECK(!p.fused);
+}
+
+static void test_ks_plan() {
+  const bool kinds[3][2] = {{false, true}, {false, false}, {true, false}};  // (wide, lz16)
+  for (u32 L = 1; L <= 9; ++L)
+    for (u32 K = 1; K <= 6; ++K)
+      for (u32 dnum = 1; dnum <= L; ++dnum)
+        for (const auto& kind : kinds) {
+          const KsShape c{L, K, dnum, (L + dnum - 1) / dnum, 1ull << 10, kind[0], kind[1]};
+          for (u32 batch : {1u, 3u})
+            for (int m = kKsFull; m <= kKsAccReady; ++m)
+              for (int ydn = 0; ydn < (m == kKsFull ? 1 : 2); ++ydn) {
+                const KsMode mode = (KsMode)m;
+                const u64 top = ks_plan(c, 0, L, batch, L, mode, ydn).total;
+                CHECK(top == ks_plan(c, 0, L, batch, 0, mode, ydn).total);
+                for (u32 level = 1; level <= L; ++level) {
+                  check_ks_plan(c, 0, level, batch, level, mode, ydn);
+                  CHECK(ks_plan(c, 0, level, batch, level, mode, ydn).total <= top);
+                }
+                // level 0 (the sharded entry points): the whole chain and a few limb windows
+                const u32 win[][2] = {{0, L}, {0, 1}, {L - 1, 1}, {L / 2, L - L / 2}, {1, L - 1}};
+                for (const auto& w : win)
+                  if (w[1] && w[0] + w[1] <= L) check_ks_plan(c, w[0], w[1], batch, 0, mode, ydn);
+              }
+        }
+}
+
 int main() {
+  test_ks_plan();
   test_moduli_and_tables();
   test_lane_major_permutation();
   test_conv_tables();

@@ -43,6 +43,28 @@ def ctx_for(fc, log_n, L, K, dnum, bits=60):
     return _CTX[key]
 
 
+GUARD = 0x5A5A5A5A5A5A5A5A
+
+
+class Guarded:
+    """An explicit workspace of exactly `nbytes` (a public fhe_*_workspace value, sized for L)
+    followed by a 4 KiB guard of a fixed pattern: runs at every level must leave the guard alone."""
+
+    def __init__(self, nbytes):
+        import torch
+
+        assert nbytes % 8 == 0
+        self.words = nbytes // 8
+        self.buf = torch.full((self.words + 512,), GUARD, dtype=torch.int64, device="cuda")
+
+    def intact(self):
+        return (self.buf[self.words:] == GUARD).all().item()
+
+
+def pass_batch(fc, ctx, batch):
+    return fc.load().fhe_keyswitch_pass_batch(ctx.handle, batch)
+
+
 def _keyswitch_level_c(fc, ctx, d2, kb, ka, level):
     """fhe_keyswitch_level itself (Context.keyswitch takes today's path at level == L)."""
     import torch
@@ -75,16 +97,23 @@ def test_keyswitch_every_level(fc, log_n, L, K, dnum, bits):
     ka = rand(ctx.all_moduli, log_n, (dnum,), seed=32)
     d = fc.to_device
     dkb, dka = d(kb), d(ka)
+    lib = fc.load()
+    guarded = {b: Guarded(lib.fhe_keyswitch_workspace(ctx.handle, L, pass_batch(fc, ctx, b)))
+               for b in (1, 3)}
     for level in range(1, L + 1):
         d2 = rand(qs[:level], log_n, (3,), seed=40 + level)
         want = [level_ref.keyswitch_level(d2[i], kb, ka, qs, ps, dnum, level) for i in range(3)]
         for batch in (1, 3):
-            ks0, ks1 = ctx.keyswitch(d(d2[:batch]), dkb, dka)
-            g0, g1 = fc.to_host(ks0), fc.to_host(ks1)
-            assert g0.shape == (batch, level, 1 << log_n)
-            for i in range(batch):
-                assert (g0[i].astype(object) == want[i][0]).all(), (level, batch, i, 0)
-                assert (g1[i].astype(object) == want[i][1]).all(), (level, batch, i, 1)
+            # the wrapper's own workspace, then exactly fhe_keyswitch_workspace bytes and a guard
+            for ws in (None, guarded[batch]):
+                ks0, ks1 = ctx.keyswitch(d(d2[:batch]), dkb, dka,
+                                         workspace=None if ws is None else ws.buf)
+                g0, g1 = fc.to_host(ks0), fc.to_host(ks1)
+                assert g0.shape == (batch, level, 1 << log_n)
+                for i in range(batch):
+                    assert (g0[i].astype(object) == want[i][0]).all(), (level, batch, i, 0)
+                    assert (g1[i].astype(object) == want[i][1]).all(), (level, batch, i, 1)
+                assert ws is None or ws.intact(), (level, batch)
     # level == L through the level entry point: fhe_keyswitch word for word
     d2 = d(rand(qs, log_n, (3,), seed=50))
     t0, t1 = ctx.keyswitch(d2, dkb, dka)
@@ -101,6 +130,7 @@ def test_mul_relin_every_level(fc, log_n, L, K, dnum):
     d = fc.to_device
     dkb, dka = d(kb), d(ka)
     batch = 2
+    ws = Guarded(fc.load().fhe_mul_relin_workspace(ctx.handle, pass_batch(fc, ctx, batch)))
     for level in range(1, L + 1):
         a = rand(qs[:level], log_n, (batch, 2), seed=60 + level)
         b = rand(qs[:level], log_n, (batch, 2), seed=70 + level)
@@ -110,10 +140,15 @@ def test_mul_relin_every_level(fc, log_n, L, K, dnum):
                     ctx.mul_relin(d(a), d(b), dkb, dka, rescale=True)
                 continue
             got = fc.to_host(ctx.mul_relin(d(a), d(b), dkb, dka, rescale=rescale))
+            # again in exactly fhe_mul_relin_workspace bytes followed by a guard
+            again = fc.to_host(ctx.mul_relin(d(a), d(b), dkb, dka, rescale=rescale,
+                                             workspace=ws.buf))
             assert got.shape == (batch, 2, level - (1 if rescale else 0), 1 << log_n)
             for i in range(batch):
                 want = level_ref.mul_relin_level(a[i], b[i], kb, ka, qs, ps, dnum, level, rescale)
                 assert (got[i].astype(object) == want).all(), (level, rescale, i)
+                assert (again[i].astype(object) == want).all(), (level, rescale, i, "explicit ws")
+            assert ws.intact(), (level, rescale)
 
 
 @pytest.mark.parametrize("log_n,L,K,dnum", [(10, 5, 2, 3), (10, 6, 2, 6)])
@@ -123,6 +158,7 @@ def test_rotate_every_level(fc, log_n, L, K, dnum):
     two_n = 2 << log_n
     sk = ctx.keygen_secret(seed=5)
     d = fc.to_device
+    ws = Guarded(fc.load().fhe_rotate_workspace(ctx.handle, pass_batch(fc, ctx, 1)))
     for g in (5, two_n - 1, pow(5, -1, two_n)):
         rb, ra = ctx.keygen_rotation(sk, g, seed=6 + g)
         hb, ha = fc.to_host(rb), fc.to_host(ra)
@@ -131,6 +167,10 @@ def test_rotate_every_level(fc, log_n, L, K, dnum):
             got = fc.to_host(ctx.rotate(d(ct), g, rb, ra))
             want = level_ref.rotate_level(ct, g, hb, ha, qs, ps, dnum, level, log_n)
             assert (got.astype(object) == want).all(), (g, level)
+            # again in exactly fhe_rotate_workspace bytes followed by a guard
+            again = fc.to_host(ctx.rotate(d(ct), g, rb, ra, workspace=ws.buf))
+            assert (again.astype(object) == want).all(), (g, level, "explicit ws")
+            assert ws.intact(), (g, level)
 
 
 def test_depth_chain_under_real_keys(fc):
@@ -213,6 +253,28 @@ def test_full_size_partial_last_digit(fc):
     for i in range(batch):
         w0, w1 = coracle.keyswitch(d2[i], skb, ska, qs[:level], ps, dnum)
         assert (g0[i] == w0).all() and (g1[i] == w1).all(), i
+
+
+def test_keyswitch_shard_with_an_empty_last_digit(fc):
+    """L = 5, dnum = 4 gives alpha = 2: digits [0, 2), [2, 4), [4, 5) are live and the fourth is
+    empty (its key rows are never read).  fhe_keyswitch_shard as a single rank (limb0 = 0,
+    nlimbs = L) on an unprepared c_all = INTT(d2), against pyoracle.keyswitch_shard, whose
+    digit_ranges drops the empty digit."""
+    log_n, L, K, dnum, batch = 10, 5, 2, 4, 2
+    ctx = ctx_for(fc, log_n, L, K, dnum)
+    qs, ps = ctx.moduli, ctx.all_moduli[L:]
+    assert pyoracle.digit_ranges(L, dnum) == [(0, 2), (2, 4), (4, 5)]
+    kb = rand(ctx.all_moduli, log_n, (dnum,), seed=97)
+    ka = rand(ctx.all_moduli, log_n, (dnum,), seed=98)
+    d2 = rand(qs, log_n, (batch,), seed=99)
+    d = fc.to_device
+    c_all = ctx.intt(d(d2))
+    k0, k1 = ctx.keyswitch_shard(c_all, d(d2), d(kb), d(ka), 0)
+    g0, g1 = fc.to_host(k0), fc.to_host(k1)
+    for i in range(batch):
+        w0, w1 = pyoracle.keyswitch_shard(coracle.ntt_inv(d2[i], qs), d2[i], kb, ka, qs, ps, dnum,
+                                          0, L)
+        assert (g0[i].astype(object) == w0).all() and (g1[i].astype(object) == w1).all(), i
 
 
 def test_in_place_and_shifted_overlap(fc):
