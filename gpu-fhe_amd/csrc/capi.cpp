@@ -792,33 +792,41 @@ int fhe_encode_roots(uint32_t log_n, double* out) {
   return kOk;
 }
 
-int fhe_encode(const fhe_ctx* c, uint64_t* out, const double* slots, double delta, uint32_t level,
-               int special, uint32_t count, void* ws, fhe_stream_t s) {
+// fhe_encode and fhe_encode_sparse (log_slots < 0: full packing, log_n - 1)
+static int encode_call(const char* who, const fhe_ctx* c, uint64_t* out, const double* slots,
+                       double delta, int64_t log_slots, uint32_t level, int special,
+                       uint32_t count, void* ws, fhe_stream_t s) {
+  const std::string w(who);
   // (the scale first: it needs no context, so a CPU-only machine can check the refusal)
   if (!(std::isfinite(delta) && delta > 0)) {
-    set_error("fhe_encode: delta must be finite and positive");
+    set_error(w + ": delta must be finite and positive");
     return kInvalid;
   }
   if (!c) {
-    set_error("fhe_encode: null context");
+    set_error(w + ": null context");
+    return kInvalid;
+  }
+  if (log_slots < 0) log_slots = c->log_n - 1;
+  if (log_slots > (int64_t)c->log_n - 1) {
+    set_error(w + ": log_slots must be in [0, log_n - 1]");
     return kInvalid;
   }
   if (level == 0 || level > c->L) {
-    set_error("fhe_encode: level must be in [1, L]");
+    set_error(w + ": level must be in [1, L]");
     return kInvalid;
   }
   if (special && c->K == 0) {
-    set_error("fhe_encode: special needs a context with P-limbs (K > 0)");
+    set_error(w + ": special needs a context with P-limbs (K > 0)");
     return kInvalid;
   }
   if (!out || !slots) {
-    set_error("fhe_encode: null data pointer");
+    set_error(w + ": null data pointer");
     return kInvalid;
   }
   const uint64_t rows = level + (special ? c->K : 0);
   if (spans_overlap(out, (uint64_t)count * rows * c->n, reinterpret_cast<const uint64_t*>(slots),
-                    (uint64_t)count * c->n)) {
-    set_error("fhe_encode: out overlaps slots");
+                    (uint64_t)count << (log_slots + 1))) {
+    set_error(w + ": out overlaps slots");
     return kInvalid;
   }
   if (count == 0) return kOk;
@@ -827,46 +835,77 @@ int fhe_encode(const fhe_ctx* c, uint64_t* out, const double* slots, double delt
   // FHECORE_ENCODE_UNFUSED=1: the separate-spread form of wide contexts on any context (the same
   // bits; tools/encode_times.py times the two against each other)
   const char* u = std::getenv("FHECORE_ENCODE_UNFUSED");
-  return launch_encode(c, out, slots, delta, level, special != 0, count, ws, u && u[0] == '1',
-                       hs(s));
+  return launch_encode(c, out, slots, delta, (uint32_t)log_slots, level, special != 0, count, ws,
+                       u && u[0] == '1', hs(s));
+}
+
+int fhe_encode(const fhe_ctx* c, uint64_t* out, const double* slots, double delta, uint32_t level,
+               int special, uint32_t count, void* ws, fhe_stream_t s) {
+  return encode_call("fhe_encode", c, out, slots, delta, -1, level, special, count, ws, s);
+}
+
+int fhe_encode_sparse(const fhe_ctx* c, uint64_t* out, const double* slots, double delta,
+                      uint32_t log_slots, uint32_t level, int special, uint32_t count, void* ws,
+                      fhe_stream_t s) {
+  return encode_call("fhe_encode_sparse", c, out, slots, delta, log_slots, level, special, count,
+                     ws, s);
 }
 
 size_t fhe_decode_workspace(const fhe_ctx* c, uint32_t count) {
   return c ? decode_workspace_bytes(c, count) : 0;
 }
 
-int fhe_decode(const fhe_ctx* c, double* slots, const uint64_t* pt, double delta, uint32_t pt_rows,
-               uint32_t level, uint32_t count, void* ws, fhe_stream_t s) {
+static int decode_call(const char* who, const fhe_ctx* c, double* slots, const uint64_t* pt,
+                       double delta, int64_t log_slots, uint32_t pt_rows, uint32_t level,
+                       uint32_t count, void* ws, fhe_stream_t s) {
+  const std::string w(who);
   // (the scale first: it needs no context, so a CPU-only machine can check the refusal)
   if (!(std::isfinite(delta) && delta > 0)) {
-    set_error("fhe_decode: delta must be finite and positive");
+    set_error(w + ": delta must be finite and positive");
     return kInvalid;
   }
   if (!c) {
-    set_error("fhe_decode: null context");
+    set_error(w + ": null context");
+    return kInvalid;
+  }
+  if (log_slots < 0) log_slots = c->log_n - 1;
+  if (log_slots > (int64_t)c->log_n - 1) {
+    set_error(w + ": log_slots must be in [0, log_n - 1]");
     return kInvalid;
   }
   if (level == 0 || level > c->L) {
-    set_error("fhe_decode: level must be in [1, L]");
+    set_error(w + ": level must be in [1, L]");
     return kInvalid;
   }
   if (pt_rows < std::min<uint32_t>(level, 2)) {
-    set_error("fhe_decode: pt_rows must cover the limbs read (min(level, 2))");
+    set_error(w + ": pt_rows must cover the limbs read (min(level, 2))");
     return kInvalid;
   }
   if (!slots || !pt) {
-    set_error("fhe_decode: null data pointer");
+    set_error(w + ": null data pointer");
     return kInvalid;
   }
-  if (spans_overlap(reinterpret_cast<const uint64_t*>(slots), (uint64_t)count * c->n, pt,
-                    (uint64_t)count * pt_rows * c->n)) {
-    set_error("fhe_decode: slots overlaps pt");
+  if (spans_overlap(reinterpret_cast<const uint64_t*>(slots), (uint64_t)count << (log_slots + 1),
+                    pt, (uint64_t)count * pt_rows * c->n)) {
+    set_error(w + ": slots overlaps pt");
     return kInvalid;
   }
   if (count == 0) return kOk;
   int rc = ensure_ws(c, decode_workspace_bytes(c, count), &ws, hs(s));
   if (rc) return rc;
-  return launch_decode(c, slots, pt, delta, pt_rows, level, count, ws, hs(s));
+  return launch_decode(c, slots, pt, delta, (uint32_t)log_slots, pt_rows, level, count, ws, hs(s));
+}
+
+int fhe_decode(const fhe_ctx* c, double* slots, const uint64_t* pt, double delta, uint32_t pt_rows,
+               uint32_t level, uint32_t count, void* ws, fhe_stream_t s) {
+  return decode_call("fhe_decode", c, slots, pt, delta, -1, pt_rows, level, count, ws, s);
+}
+
+int fhe_decode_sparse(const fhe_ctx* c, double* slots, const uint64_t* pt, double delta,
+                      uint32_t log_slots, uint32_t pt_rows, uint32_t level, uint32_t count,
+                      void* ws, fhe_stream_t s) {
+  return decode_call("fhe_decode_sparse", c, slots, pt, delta, log_slots, pt_rows, level, count,
+                     ws, s);
 }
 
 }  // extern "C"

@@ -15,6 +15,10 @@
 // the bit reversal, the scaling and the rounding into the contiguous pass's stores; decode
 // (decimation in time, len = 2 .. n) folds the bit reversal into the contiguous pass's loads and
 // the division by delta into the strided pass's stores.
+//
+// Sparse packing (fhe_encode_sparse / fhe_decode_sparse, n_s < N / 2 slots) is the same network on
+// n_s points with the same tables, in a kernel of its own (k_sfft_sparse, below): the dense
+// kernel and its launches stay what they were.
 #pragma clang fp contract(off)
 
 #include <cmath>
@@ -50,6 +54,23 @@ struct FftPass {
 };
 
 __device__ __forceinline__ u32 brev(u32 x, u32 bits) { return __brev(x) >> (32 - bits); }
+
+// One butterfly in place: ENC (a, b) -> (a + b, (a - b) w), else (a, b) -> (a + b w, a - b w).
+template <bool ENC>
+__device__ __forceinline__ void butterfly(double2& a, double2& b, const double2 w) {
+  const double2 x = a, y = b;
+  if (ENC) {
+    a = make_double2(x.x + y.x, x.y + y.y);
+    const double dr = x.x - y.x, di = x.y - y.y;
+    const double p1 = dr * w.x, p2 = di * w.y, p3 = dr * w.y, p4 = di * w.x;
+    b = make_double2(p1 - p2, p3 + p4);
+  } else {
+    const double p1 = y.x * w.x, p2 = y.y * w.y, p3 = y.x * w.y, p4 = y.y * w.x;
+    const double br = p1 - p2, bi = p3 + p4;
+    a = make_double2(x.x + br, x.y + bi);
+    b = make_double2(x.x - br, x.y - bi);
+  }
+}
 
 // ENC: the inverse special FFT of encode; otherwise the forward one of decode.
 template <bool ENC>
@@ -91,21 +112,7 @@ __global__ __launch_bounds__(kFftThreads) void k_sfft_pass(const FftPass a) {
       const u32 j = gidx(ea) & ((1u << gb) - 1);
       const u32 r = a.rot[j] & lqm;
       const double2 w = a.roots[(ENC ? lqm + 1 - r : r) << wsh];
-      const double2 x = lds[lpad(ea)], y = lds[lpad(eb)];
-      double2 s, d;
-      if (ENC) {
-        s = make_double2(x.x + y.x, x.y + y.y);
-        const double dr = x.x - y.x, di = x.y - y.y;
-        const double p1 = dr * w.x, p2 = di * w.y, p3 = dr * w.y, p4 = di * w.x;
-        d = make_double2(p1 - p2, p3 + p4);
-      } else {
-        const double p1 = y.x * w.x, p2 = y.y * w.y, p3 = y.x * w.y, p4 = y.y * w.x;
-        const double br = p1 - p2, bi = p3 + p4;
-        s = make_double2(x.x + br, x.y + bi);
-        d = make_double2(x.x - br, x.y - bi);
-      }
-      lds[lpad(ea)] = s;
-      lds[lpad(eb)] = d;
+      butterfly<ENC>(lds[lpad(ea)], lds[lpad(eb)], w);
     }
     __syncthreads();
   }
@@ -181,6 +188,189 @@ int launch_sfft(const fhe_ctx* c, const void* in, void* out, double2* work, doub
   return launch_pass<ENC>(second, count, s);
 }
 
+// ---- sparse packing: n_s = 2^ls slots, ls <= log_n - 2, gap = N / (2 n_s) = 2^lg >= 2 ----------
+// The transform is the same network on n_s points with the ring's own tables: rot[j] mod lq is
+// 5^j mod lq whatever the ring, and W_s[k] = W[k gap], so only the twiddle shift changes
+// (log_n - 2 - gb: FftPass::ln is now the slot count's logarithm and no longer gives it).
+//
+// One pass (ls <= kTileLog): a tile holds 2^P whole plaintexts next to each other, element
+// e = (q, point); their stages are independent and share j, so the butterfly loop is the dense
+// one on 2^(ls + P) elements.  The last tile may hold fewer than 2^P plaintexts (zero-filled,
+// not stored).  Two passes (ls > kTileLog): P = 0 and the tiles are the dense kernel's with
+// n_s for n.
+//
+// Encode's rounding store writes whole runs: coefficient k gap and the gap - 1 zeros behind it,
+// so the coefficients [count][N] need no memset and the lift reads nothing unwritten.  The loop
+// runs over the tile's *output* coefficients in ascending order (lane i -> coefficient rank i,
+// the point found through the bit reversal), so a wave's 64 stores are 512 contiguous bytes
+// (one pass) or whole runs (two passes, where a tile's points are 2^(ls - kTileLog) runs apart).
+// A tile's outputs are 2^(P + log_n) coefficients, far more than its 2^T points: above
+// 2^kStoreLog of them the store is cut into 2^S slices, one workgroup each, every one of which
+// redoes the tile's (small) transform -- few workgroups writing megabytes each is what makes a
+// small transform slower than the dense one otherwise.  For the same reason P stops where a
+// tile's outputs reach 2^kStoreLog.
+constexpr u32 kStoreLog = 13;
+
+struct SparsePass {
+  FftPass f;   // ln = ls, T = log2 of a plaintext's points in the tile, tiles = n_s >> T
+  u32 wbase;   // log_n - 2: the twiddle shift of the stage lh = 2^gb is wbase - gb
+  u32 lg;      // log2 gap
+  u32 P;       // log2 of the plaintexts per tile
+  u32 S;       // log2 of the store slices per tile (kOutRound)
+  u32 count;
+};
+
+__device__ __forceinline__ u32 brev0(u32 x, u32 bits) { return bits ? brev(x, bits) : 0; }
+
+template <bool ENC>
+__global__ __launch_bounds__(kFftThreads) void k_sfft_sparse(const SparsePass sp) {
+  __shared__ double2 lds[kTileLds];
+  const FftPass& a = sp.f;
+  const u32 n = 1u << a.ln, Tp = a.T, T = Tp + sp.P, C = a.C;
+  const u32 sl = blockIdx.x & ((1u << sp.S) - 1), blk = blockIdx.x >> sp.S;
+  const u32 tl = blk % a.tiles, p0 = (blk / a.tiles) << sp.P;
+  const bool strided = C < Tp;
+  const u32 lc_bits = strided ? a.b_lo - C : 0;
+  const u32 base = strided ? ((tl >> lc_bits) << (a.b_lo + a.B)) + ((tl & ((1u << lc_bits) - 1)) << C)
+                           : tl << Tp;
+  const u32 cmask = (1u << C) - 1, pmask = (1u << Tp) - 1;
+  const u32 lb = strided ? C : 0;
+  // tile element (q, e) -> point of plaintext p0 + q
+  auto gidx = [&](u32 e) {
+    e &= pmask;
+    return strided ? base + ((e >> C) << a.b_lo) + (e & cmask) : base + e;
+  };
+
+  for (u32 e = threadIdx.x; e < (1u << T); e += kFftThreads) {
+    const u32 g = gidx(e), p = p0 + (e >> Tp);
+    double2 v = make_double2(0.0, 0.0);
+    if (p < sp.count) {
+      if (a.in_mode == kInCoeff) {
+        const double* x = static_cast<const double*>(a.in) + (u64)p * 2 * n;
+        const u32 k = brev0(g, a.ln);
+        v = make_double2(x[k], x[k + n]);
+      } else {
+        v = static_cast<const double2*>(a.in)[(u64)p * n + g];
+      }
+    }
+    lds[lpad(e)] = v;
+  }
+  __syncthreads();
+
+  for (u32 st = 0; st < a.B; ++st) {
+    const u32 i = ENC ? a.B - 1 - st : st;
+    const u32 pb = lb + i;
+    const u32 gb = a.b_lo + i;
+    const u32 lqm = (8u << gb) - 1, wsh = sp.wbase - gb;
+    for (u32 k = threadIdx.x; k < (1u << (T - 1)); k += kFftThreads) {
+      const u32 ea = ((k >> pb) << (pb + 1)) | (k & ((1u << pb) - 1));
+      const u32 eb = ea + (1u << pb);
+      const u32 j = gidx(ea) & ((1u << gb) - 1);
+      const u32 r = a.rot[j] & lqm;
+      const double2 w = a.roots[(ENC ? lqm + 1 - r : r) << wsh];
+      butterfly<ENC>(lds[lpad(ea)], lds[lpad(eb)], w);
+    }
+    __syncthreads();
+  }
+
+  if (a.out_mode == kOutRound) {
+    // output rank o = (q, im, kk, r): coefficient ((im n_s + k) gap + r) of plaintext p0 + q,
+    // k = (kk, bitrev(tl)) the bit reversal of the point (tl, bitrev(kk))
+    const u32 lo_bits = a.ln - Tp, klo = brev0(tl, lo_bits);
+    const u32 log_n = a.ln + 1 + sp.lg, per = T + 1 + sp.lg - sp.S;
+    long long* c = static_cast<long long*>(a.out);
+    for (u32 i = threadIdx.x; i < (1u << per); i += kFftThreads) {
+      const u32 o = (sl << per) + i;
+      const u32 t = o >> sp.lg, q = t >> (Tp + 1);
+      if (p0 + q >= sp.count) break;  // ranks ascend in q
+      const u32 kk = t & pmask, im = (t >> Tp) & 1;
+      long long val = 0;
+      if ((o & ((1u << sp.lg) - 1)) == 0) {
+        const double2 v = lds[lpad((q << Tp) | brev0(kk, Tp))];
+        val = (long long)rint((im ? v.y : v.x) * a.scale);
+      }
+      const u64 k = ((u64)kk << lo_bits) | klo;
+      c[((u64)(p0 + q) << log_n) + ((((u64)im << a.ln) + k) << sp.lg) + (o & ((1u << sp.lg) - 1))] =
+          val;
+    }
+    return;
+  }
+  for (u32 e = threadIdx.x; e < (1u << T); e += kFftThreads) {
+    const u32 g = gidx(e), p = p0 + (e >> Tp);
+    if (p >= sp.count) break;
+    const double2 v = lds[lpad(e)];
+    static_cast<double2*>(a.out)[(u64)p * n + g] =
+        a.out_mode == kOutDivide ? make_double2(v.x / a.scale, v.y / a.scale) : v;
+  }
+}
+
+template <bool ENC>
+int launch_sparse_pass(const SparsePass& sp, hipStream_t s) {
+  const u64 groups = ((u64)sp.count + (1u << sp.P) - 1) >> sp.P;
+  const u64 blocks = (groups * sp.f.tiles) << sp.S;
+  if (int rc = check_grid(blocks, kFftThreads, 1, 1, ENC ? "encode" : "decode")) return rc;
+  k_sfft_sparse<ENC><<<dim3((u32)blocks), kFftThreads, 0, s>>>(sp);
+  FHE_HIP_CHECK(hipGetLastError());
+  return kOk;
+}
+
+// launch_sfft on 2^ls < N / 2 slots: ENC slots [count][n_s] -> int64 coefficients [count][N]
+// (scale = delta / n_s), else doubles [count][2 n_s] -> slots (scale = delta).
+template <bool ENC>
+int launch_sfft_sparse(const fhe_ctx* c, const void* in, void* out, double2* work, double scale,
+                       u32 ls, u32 count, hipStream_t s) {
+  SparsePass sp{};
+  sp.f.roots = c->d_enc_roots;
+  sp.f.rot = c->d_enc_rot;
+  sp.f.scale = scale;
+  sp.f.ln = ls;
+  sp.f.T = std::min<u32>(ls, kTileLog);
+  sp.f.tiles = 1u << (ls - sp.f.T);
+  sp.wbase = c->log_n - 2;
+  sp.lg = c->log_n - 1 - ls;
+  sp.count = count;
+  SparsePass contiguous = sp;
+  contiguous.f.C = sp.f.T;
+  contiguous.f.b_lo = 0;
+  contiguous.f.B = sp.f.T;
+  // the slices of the contiguous pass's rounding store (its tile holds 2^P plaintexts)
+  auto slices = [&](SparsePass& x) {
+    const u32 outs = x.f.T + x.P + 1 + x.lg;
+    x.S = outs > kStoreLog ? outs - kStoreLog : 0;
+  };
+  if (ls <= (u32)kTileLog) {
+    SparsePass x = contiguous;
+    u32 cl = 0;  // ceil(log2 count)
+    while ((1u << cl) < count && cl < (u32)kTileLog) ++cl;
+    x.P = std::min<u32>(kTileLog - ls, cl);
+    if (ENC) {
+      x.P = std::min<u32>(x.P, c->log_n < kStoreLog ? kStoreLog - c->log_n : 0);
+      slices(x);
+    }
+    x.f.in = in;
+    x.f.out = out;
+    x.f.in_mode = ENC ? kInComplex : kInCoeff;
+    x.f.out_mode = ENC ? kOutRound : kOutDivide;
+    return launch_sparse_pass<ENC>(x, s);
+  }
+  SparsePass strided = sp;
+  strided.f.B = ls - kTileLog;
+  strided.f.C = kTileLog - strided.f.B;
+  strided.f.b_lo = kTileLog;
+  if (ENC) slices(contiguous);
+  SparsePass first = ENC ? strided : contiguous, second = ENC ? contiguous : strided;
+  first.f.in = in;
+  first.f.out = work;
+  first.f.in_mode = ENC ? kInComplex : kInCoeff;
+  first.f.out_mode = kOutComplex;
+  second.f.in = work;
+  second.f.out = out;
+  second.f.in_mode = kInComplex;
+  second.f.out_mode = ENC ? kOutRound : kOutDivide;
+  if (int rc = launch_sparse_pass<ENC>(first, s)) return rc;
+  return launch_sparse_pass<ENC>(second, s);
+}
+
 // The unfused lift (wide contexts): coefficients [count][N] -> out [count][rows][N], canonical
 // residues of every row's limb, to be NTT'd in place.  Grid y = row, z = plaintext.
 __global__ __launch_bounds__(kFftThreads) void k_encode_spread(u64* __restrict__ out,
@@ -198,13 +388,9 @@ __global__ __launch_bounds__(kFftThreads) void k_encode_spread(u64* __restrict__
 
 // Decode's centring: x [count][nl][N] = INTT of limb 0 (and limb 1 when nl == 2) -> the centred
 // value over q_0 (q_0 q_1) as one round-to-nearest-even double, d [count][N].
-__global__ __launch_bounds__(kFftThreads) void k_decode_centre(double* __restrict__ d,
-                                                               const u64* __restrict__ x, u32 nl,
-                                                               u32 log_n, ulonglong2 q0inv,
-                                                               const ModParams* __restrict__ mods) {
-  const u64 n = 1ull << log_n;
-  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  const u64 p = blockIdx.y;
+__device__ __forceinline__ double centre_value(const u64* __restrict__ x, u64 p, u64 i, u32 nl,
+                                               u64 n, ulonglong2 q0inv,
+                                               const ModParams* __restrict__ mods) {
   const u64 q0 = mods[0].q;
   const u64 x0 = x[(p * nl) * n + i];
   u128 mag;
@@ -235,7 +421,27 @@ __global__ __launch_bounds__(kFftThreads) void k_decode_centre(double* __restric
     if ((u64)mag << (64 - sh)) w |= 1;
     v = ldexp((double)w, sh);
   }
-  d[p * n + i] = neg ? -v : v;
+  return neg ? -v : v;
+}
+
+__global__ __launch_bounds__(kFftThreads) void k_decode_centre(double* __restrict__ d,
+                                                               const u64* __restrict__ x, u32 nl,
+                                                               u32 log_n, ulonglong2 q0inv,
+                                                               const ModParams* __restrict__ mods) {
+  const u64 n = 1ull << log_n;
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u64 p = blockIdx.y;
+  d[p * n + i] = centre_value(x, p, i, nl, n, q0inv, mods);
+}
+
+// The same of the coefficients k gap only (sparse packing): d [count][2 n_s], 2 n_s = N >> lg.
+__global__ __launch_bounds__(kFftThreads) void k_decode_centre_sparse(
+    double* __restrict__ d, const u64* __restrict__ x, u32 nl, u32 log_n, u32 lg,
+    ulonglong2 q0inv, const ModParams* __restrict__ mods) {
+  const u64 n = 1ull << log_n, m = n >> lg;
+  const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u64 p = blockIdx.y;
+  if (k < m) d[p * m + k] = centre_value(x, p, k << lg, nl, n, q0inv, mods);
 }
 
 }  // namespace
@@ -250,16 +456,19 @@ size_t decode_workspace_bytes(const fhe_ctx* c, u32 count) {
   return (size_t)3 * count * c->n * sizeof(u64);
 }
 
-int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta, u32 level,
-                  bool special, u32 count, void* ws, bool unfused, hipStream_t s) {
+int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta, u32 log_slots,
+                  u32 level, bool special, u32 count, void* ws, bool unfused, hipStream_t s) {
   if (count == 0) return kOk;
   const u64 n = c->n;
   const u32 rows = level + (special ? c->K : 0);
   double2* work = static_cast<double2*>(ws);
   long long* cf = reinterpret_cast<long long*>(static_cast<u64*>(ws) + (u64)count * n);
-  const double scale = delta / (double)(n / 2);
+  const bool full = log_slots == c->log_n - 1;
+  const double scale = delta / (double)(1ull << log_slots);
   int rc;
-  if ((rc = launch_sfft<true>(c, slots, cf, work, scale, count, s))) return rc;
+  if ((rc = full ? launch_sfft<true>(c, slots, cf, work, scale, count, s)
+                 : launch_sfft_sparse<true>(c, slots, cf, work, scale, log_slots, count, s)))
+    return rc;
   prof_mark(s, "encode_fft");
   const u64 ps = (u64)rows * n;
   if (!c->wide && !unfused) {
@@ -285,8 +494,8 @@ int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta,
   return kOk;
 }
 
-int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 pt_rows,
-                  u32 level, u32 count, void* ws, hipStream_t s) {
+int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 log_slots,
+                  u32 pt_rows, u32 level, u32 count, void* ws, hipStream_t s) {
   if (count == 0) return kOk;
   const u64 n = c->n;
   const u32 nl = level >= 2 ? 2 : 1;
@@ -296,13 +505,24 @@ int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, 
   if ((rc = launch_ntt_strided(c, false, pt, (u64)pt_rows * n, x, (u64)nl * n, count, 0, nl, s)))
     return rc;
   prof_mark(s, "decode_intt");
-  if ((rc = check_grid(n / kFftThreads, kFftThreads, count, 1, "decode"))) return rc;
-  k_decode_centre<<<dim3((u32)(n / kFftThreads), count), kFftThreads, 0, s>>>(
-      d, x, nl, c->log_n, c->enc_q0inv, c->d_mods);
+  const bool full = log_slots == c->log_n - 1;
+  if (full) {
+    if ((rc = check_grid(n / kFftThreads, kFftThreads, count, 1, "decode"))) return rc;
+    k_decode_centre<<<dim3((u32)(n / kFftThreads), count), kFftThreads, 0, s>>>(
+        d, x, nl, c->log_n, c->enc_q0inv, c->d_mods);
+  } else {
+    const u32 lg = c->log_n - 1 - log_slots;
+    const u32 bx = (u32)(((n >> lg) + kFftThreads - 1) / kFftThreads);
+    if ((rc = check_grid(bx, kFftThreads, count, 1, "decode"))) return rc;
+    k_decode_centre_sparse<<<dim3(bx, count), kFftThreads, 0, s>>>(d, x, nl, c->log_n, lg,
+                                                                    c->enc_q0inv, c->d_mods);
+  }
   FHE_HIP_CHECK(hipGetLastError());
   prof_mark(s, "decode_centre");
   // x is dead: its region is the FFT's workspace
-  if ((rc = launch_sfft<false>(c, d, slots, reinterpret_cast<double2*>(x), delta, count, s)))
+  double2* work = reinterpret_cast<double2*>(x);
+  if ((rc = full ? launch_sfft<false>(c, d, slots, work, delta, count, s)
+                 : launch_sfft_sparse<false>(c, d, slots, work, delta, log_slots, count, s)))
     return rc;
   prof_mark(s, "decode_fft");
   return kOk;

@@ -507,12 +507,16 @@ size_t linear_transform_workspace_bytes(const fhe_ctx* c, u32 n2, u32 batch);
 // slots [count][N/2][2] doubles (re, im) -> out [count][level (+ K)][N] NTT form: the inverse
 // special FFT, c = rint(v delta / (N/2)), row r = NTT(c mod q_limb(r)).  unfused: a spread kernel
 // and whole NTTs (the form of wide contexts) on any context (tools/encode_times.py measures it).
-int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta, u32 level,
-                  bool special, u32 count, void* ws, bool unfused, hipStream_t s);
+// log_slots <= log_n - 1: 2^log_slots slots per plaintext (sparse packing: the message lives in
+// Z[Y]/(Y^(2 n_s) + 1), Y = X^gap, gap = N / (2 n_s)); log_n - 1 is full packing and takes the
+// launches it always took.
+int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta, u32 log_slots,
+                  u32 level, bool special, u32 count, void* ws, bool unfused, hipStream_t s);
 size_t encode_workspace_bytes(const fhe_ctx* c, u32 count);
-// pt [count][pt_rows][N] NTT form (limbs 0 and, at level >= 2, 1 read) -> slots [count][N/2][2]
-int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 pt_rows,
-                  u32 level, u32 count, void* ws, hipStream_t s);
+// pt [count][pt_rows][N] NTT form (limbs 0 and, at level >= 2, 1 read) -> slots
+// [count][2^log_slots][2]; below full packing only the coefficients at the multiples of gap are read
+int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 log_slots,
+                  u32 pt_rows, u32 level, u32 count, void* ws, hipStream_t s);
 size_t decode_workspace_bytes(const fhe_ctx* c, u32 count);
 
 // ---- launchers (pipeline.hip): SURVEY.md §8(f) row 4 -----------------------------------

@@ -110,6 +110,10 @@ SIGNATURES = {
     "fhe_encode": (_i32, [_vp, _vp, _vp, ctypes.c_double, _u32, _i32, _u32, _vp, _vp]),
     "fhe_decode_workspace": (_sz, [_vp, _u32]),
     "fhe_decode": (_i32, [_vp, _vp, _vp, ctypes.c_double, _u32, _u32, _u32, _vp, _vp]),
+    "fhe_encode_sparse": (_i32, [_vp, _vp, _vp, ctypes.c_double, _u32, _u32, _i32, _u32, _vp,
+                                 _vp]),
+    "fhe_decode_sparse": (_i32, [_vp, _vp, _vp, ctypes.c_double, _u32, _u32, _u32, _u32, _vp,
+                                 _vp]),
     "fhe_graph_begin": (_i32, [_vp]),
     "fhe_graph_end": (_i32, [_vp, ctypes.POINTER(_vp)]),
     "fhe_graph_launch": (_i32, [_vp, _vp]),

@@ -1,8 +1,9 @@
-"""CKKS bootstrapping for full packing (N/2 slots), composed on the host from the library's public
-calls (include/fhecore.h; no C entry of its own, like fhecore.polyeval):
+"""CKKS bootstrapping for full packing (N/2 slots) and sparse packing (n_s = 2^log_slots slots),
+composed on the host from the library's public calls (include/fhecore.h; no C entry of its own,
+like fhecore.polyeval):
 
-    mod_raise -> CoeffToSlot -> conjugate + conj_split -> eval_mod (batch of 2) -> conj_merge
-              -> SlotToCoeff
+    mod_raise [-> SubSum] -> CoeffToSlot -> conjugate + conj_split -> eval_mod (batch of 2)
+              -> conj_merge -> SlotToCoeff
 
     dft_factors(log_n, groups, inverse)      the CoeffToSlot / SlotToCoeff matrices as diagonals
     place_strided_diagonals(...)             their baby-step / giant-step layout (host, numpy)
@@ -31,6 +32,21 @@ Fraction), which is the input's scale up to the evaluator's drift (~2^-30).  Eve
 diagonals are encoded at the scale of the prime its rescale divides by, so a linear transform and
 its rescale leave the declared scale where it was, exactly.
 
+Sparse packing (BootstrapParams.log_slots < log_n - 1).  The message is a polynomial in Y = X^gap,
+gap = N / (2 n_s), and the ciphertext's slot vector is n_s-periodic.  ModRaise leaves
+t = m(Y) + q_0 I(X) with I spread over all N coefficients; SubSum,
+    acc = t;  for i < log2(gap):  acc <- acc + sigma_{5^(n_s 2^i)}(acc)    (a rotation by n_s 2^i),
+is the trace onto the subring: gap t[k gap] at the multiples of gap and 0 elsewhere, that is
+gap (m(Y) + q_0 I'(Y)) with I'_k = I_{k gap}, so |I'| <= (h + 2) / 2, K and h <= 2K - 4 stand.
+The two transforms are the stage network of the ring of degree 2 n_s (dft_factors(...,
+log_slots): log_slots stages, tables sliced from the ring's, W_s[k] = W[k gap] and
+5^j mod 4 n_s = rot[j] mod 4 n_s) as length-n_s diagonals; encoded sparsely they are those
+diagonals tiled gap times, and their rotation steps are taken on the full ring (on a periodic
+vector the steps k and k - n_s act alike).  The inverse network of a periodic slot vector gives
+n_s times the Y-coefficients, SubSum gave gap: n_s gap = n, so the CoeffToSlot constant
+delta / (2 n K q_0) and every scale rule above are those of full packing.  The result is a sparse
+ciphertext: it decodes with log_slots.
+
 The secret must be sparse: |I| <= (h + 2) / 2 must stay within eval_mod's K - 1, so h <= 2K - 4
 (Context.keygen_secret(hamming_weight=h)).
 
@@ -39,10 +55,13 @@ vectors only, so GpuBackend (below) and a CPU restatement compute the same bits.
 polyeval's calls (moduli, mul_relin, lincomb, drop_level) plus
     log_n                                    the ring degree's logarithm
     mod_raise(a, level)                      a at any level -> `level` limbs
-    load_factor(z, baby, giant, delta)       z complex [n2, n1, n] -> a handle for linear_transform
+    load_factor(z, baby, giant, delta)       z complex [n2, n1, n] (sparse packing: [n2, n1, n_s],
+                                             encoded as the tiled vector) -> a handle for
+                                             linear_transform
                                              (the plaintexts over Q u P and the rotation keys of
                                              the slot steps baby[b], giant[g]; step 0 takes none)
     linear_transform(a, factor), rescale(a)
+    rotate(a, step)                          the slot rotation by `step` (SubSum; sparse packing only)
     conjugate(a), conj_split(a, c), conj_merge(a, b)
     stack(a, b), unstack(x)                  a batch of 2 and back
 """
@@ -62,7 +81,9 @@ _BSGS_MAX = 16  # fhe_linear_transform: at most 16 baby steps and 16 giant steps
 
 # ----------------------------------------------------------------------------- the factors
 
-def _tables(log_n):
+def _tables(log_n, log_slots=None):
+    """(W [4 n_s], rot [n_s]) of the ring of degree 2 n_s, sliced from the table of the ring of
+    degree 2^log_n (fhe_encode_roots refuses rings below 2^10): W_s[k] = W[k gap]."""
     from .context import encode_roots
 
     n = 1 << (log_n - 1)
@@ -73,7 +94,18 @@ def _tables(log_n):
     for j in range(n):
         rot[j] = e
         e = e * 5 % (4 * n)
-    return w, rot
+    if log_slots is None or log_slots == log_n - 1:
+        return w, rot
+    ns = 1 << log_slots
+    return w[::n // ns], rot[:ns] % (4 * ns)
+
+
+def _slot_bits(log_n, log_slots):
+    if log_slots is None:
+        return log_n - 1
+    if not 0 <= log_slots <= log_n - 1:
+        raise ValueError(f"log_slots must be in [0, {log_n - 1}]")
+    return int(log_slots)
 
 
 def _stage(n, ln, w, rot, inverse):
@@ -105,11 +137,10 @@ def _compose(a, b):
     return out
 
 
-def stage_lengths(log_n, inverse):
-    """Block lengths of the stage network in the order of application."""
-    n = 1 << (log_n - 1)
-    lens = [1 << s for s in range(1, log_n)]  # 2 .. n
-    assert lens[-1] == n
+def stage_lengths(log_n, inverse, log_slots=None):
+    """Block lengths of the stage network in the order of application (log_slots: of the ring of
+    degree 2^(log_slots + 1), 2 .. n_s)."""
+    lens = [1 << s for s in range(1, _slot_bits(log_n, log_slots) + 1)]  # 2 .. n
     return lens[::-1] if inverse else lens
 
 
@@ -121,14 +152,16 @@ def group_sizes(stages, groups):
     return [q + 1] * r + [q] * (groups - r)
 
 
-def dft_factors(log_n, groups, inverse):
+def dft_factors(log_n, groups, inverse, log_slots=None):
     """The special FFT's stage network as `groups` slot matrices, first applied first: a list of
     {diagonal index: complex128 [N/2]}.  inverse=True is CoeffToSlot (fhe_encode's stages,
     len = n .. 2), inverse=False SlotToCoeff (fhe_decode's, len = 2 .. n); neither includes the
-    bit-reversal.  SlotToCoeff o CoeffToSlot = n id."""
-    n = 1 << (log_n - 1)
-    w, rot = _tables(log_n)
-    lens = stage_lengths(log_n, inverse)
+    bit-reversal.  SlotToCoeff o CoeffToSlot = n id.  log_slots: the network of the ring of degree
+    2^(log_slots + 1) as length-n_s diagonals, its tables sliced from the ring's; tiled
+    N / 2^(log_slots + 1) times they act on the n_s-periodic slot vectors of the full ring."""
+    n = 1 << _slot_bits(log_n, log_slots)
+    w, rot = _tables(log_n, log_slots)
+    lens = stage_lengths(log_n, inverse, log_slots)
     out, at = [], 0
     for size in group_sizes(len(lens), groups):
         f = _stage(n, lens[at], w, rot, inverse)
@@ -139,13 +172,14 @@ def dft_factors(log_n, groups, inverse):
     return out
 
 
-def factor_layouts(log_n, groups, inverse):
+def factor_layouts(log_n, groups, inverse, log_slots=None):
     """(n1, n2, stride, offset) per factor of dft_factors: s merged stages whose smallest half
     length is `stride` have the diagonals stride * a, |a| <= 2^s - 1 (offset = -(2^s - 1),
     2^(s+1) - 1 of them), except the factor holding the stage len = n, where the shifts wrap and
-    a = 0 .. 2^s - 1 covers them (offset 0)."""
-    n = 1 << (log_n - 1)
-    lens = stage_lengths(log_n, inverse)
+    a = 0 .. 2^s - 1 covers them (offset 0).  log_slots: n = n_s; the steps are taken on the full
+    ring, where on an n_s-periodic vector k and k - n_s act alike."""
+    n = 1 << _slot_bits(log_n, log_slots)
+    lens = stage_lengths(log_n, inverse, log_slots)
     out, at = [], 0
     for s in group_sizes(len(lens), groups):
         grp = lens[at:at + s]
@@ -239,7 +273,9 @@ class GpuBackend(polyeval.GpuBackend):
 
     def load_factor(self, z, baby, giant, delta):
         c = self.ctx
-        enc = c.encode(z, delta, level=c.L, special=True)
+        ns = z.shape[-1]
+        sparse = None if ns == c.n // 2 else ns.bit_length() - 1
+        enc = c.encode(z, delta, level=c.L, special=True, log_slots=sparse)
         be, ge = [c.galois_elt(s) for s in baby], [c.galois_elt(s) for s in giant]
         pts = [[enc[g, b] for b in range(len(be))] for g in range(len(ge))]
         return (be, [self._key(e) for e in be], ge, [self._key(e) for e in ge], pts)
@@ -252,6 +288,10 @@ class GpuBackend(polyeval.GpuBackend):
 
     def conjugate(self, a):
         elt = 2 * self.ctx.n - 1
+        return self.ctx.rotate(a, elt, *self._key(elt))
+
+    def rotate(self, a, step):
+        elt = self.ctx.galois_elt(step)
         return self.ctx.rotate(a, elt, *self._key(elt))
 
     def conj_split(self, a, c):
@@ -280,14 +320,15 @@ class BootstrapParams:
     stc_groups: int = 3
     delta: float = 2.0 ** 50   # the scale eval_mod works at: the chain's primes sit close to it
     hamming_weight: int = 28   # the declared weight of the secret
+    log_slots: int | None = None  # sparse packing: 2^log_slots slots; None = log_n - 1, full
 
 
 class Bootstrapper:
     """bootstrap(ct) refreshes a ciphertext at any level >= 1 to level
     L - cts_groups - eval_mod_levels - stc_groups (out_level).  The constructor builds the six
     factors, has the backend encode their diagonals and make their keys once, and refuses
-    (ValueError) a declared Hamming weight above 2K - 4 and a chain too short for the result to
-    keep a level."""
+    (ValueError) a declared Hamming weight above 2K - 4, a chain too short for the result to
+    keep a level, and a log_slots outside [max(cts_groups, stc_groups), log_n - 1]."""
 
     def __init__(self, backend, params=None, **kw):
         p = params if params is not None else BootstrapParams(**kw)
@@ -308,9 +349,19 @@ class Bootstrapper:
             raise ValueError(f"Bootstrapper: the chain of {self.L} primes is too short: "
                              f"{p.cts_groups} + {self.em_levels} + {p.stc_groups} levels are "
                              "consumed and the result needs one")
+        lo = max(p.cts_groups, p.stc_groups)
+        if p.log_slots is not None and not lo <= p.log_slots <= self.log_n - 1:
+            raise ValueError(f"Bootstrapper: log_slots must be in [{lo}, {self.log_n - 1}] (a "
+                             "factor needs a stage)")
+        full = p.log_slots is None or p.log_slots == self.log_n - 1
+        self.log_slots = None if full else int(p.log_slots)
+        # SubSum: the rotations by n_s 2^i that sum the gap copies of the subring's coefficients
+        self.subsum_steps = [] if full else [
+            (1 << self.log_slots) << i for i in range(self.log_n - 1 - self.log_slots)]
         n = 1 << (self.log_n - 1)
         q0 = q[0]
-        # CoeffToSlot: total delta / (2 n K q_0); SlotToCoeff: q_0 / (2 pi delta)
+        # CoeffToSlot: total delta / (2 n K q_0); SlotToCoeff: q_0 / (2 pi delta).  Sparse: SubSum's
+        # gap times the small network's n_s is the same n
         c_cts = (p.delta / (2.0 * n * p.K * q0)) ** (1.0 / p.cts_groups)
         c_stc = (q0 / (2.0 * math.pi * p.delta)) ** (1.0 / p.stc_groups)
         lv = self.L
@@ -324,10 +375,12 @@ class Bootstrapper:
     def _load(self, inverse, groups, const, level, q):
         """The factors' handles and the exact product of what their encodings multiply the raw
         integers by, relative to the rescales that follow: prod const * float(q_l) / q_l."""
-        n = 1 << (self.log_n - 1)
+        ls = self.log_slots
+        n = 1 << (self.log_n - 1 if ls is None else ls)
         out, mult = [], Fraction(1)
-        layouts = factor_layouts(self.log_n, groups, inverse)
-        for f, (n1, n2, stride, offset) in zip(dft_factors(self.log_n, groups, inverse), layouts):
+        layouts = factor_layouts(self.log_n, groups, inverse, ls)
+        factors = dft_factors(self.log_n, groups, inverse, ls)
+        for f, (n1, n2, stride, offset) in zip(factors, layouts):
             if n1 > _BSGS_MAX or n2 > _BSGS_MAX:
                 raise ValueError(f"Bootstrapper: a factor of {n1} x {n2} baby / giant steps exceeds "
                                  f"linear_transform's {_BSGS_MAX}: use more groups")
@@ -345,14 +398,19 @@ class Bootstrapper:
         return a
 
     def bootstrap(self, ct: Ct, mark=None) -> Ct:
-        """mark: called with the phase's name after each of mod_raise, coeff_to_slot, split
-        (conjugation included), eval_mod, merge, slot_to_coeff (tools/bootstrap_times.py)."""
+        """mark: called with the phase's name after each of mod_raise, subsum (sparse packing
+        only), coeff_to_slot, split (conjugation included), eval_mod, merge, slot_to_coeff
+        (tools/bootstrap_times.py)."""
         be, p = self.be, self.p
         mark = mark or (lambda name: None)
         if not 1 <= ct.level <= self.L:
             raise ValueError(f"bootstrap: the input is at level {ct.level}, expected 1 .. {self.L}")
         a = be.mod_raise(ct.data, self.L)            # reads limb 0 only: no drop needed
         mark("mod_raise")
+        if self.subsum_steps:
+            for step in self.subsum_steps:
+                a = be.lincomb([a, be.rotate(a, step)], [1, 1], False, False, self.L)
+            mark("subsum")
         a = self._transform(a, self.cts)
         mark("coeff_to_slot")
         re, im = be.conj_split(a, be.conjugate(a))   # slots t_k / (K q_0), t_{k+n} / (K q_0)

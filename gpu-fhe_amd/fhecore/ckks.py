@@ -13,6 +13,12 @@ This class stays the mathematical definition.  The device path -- Context.encode
 encode_diagonals (fhe_encode / fhe_decode) -- computes the same embedding with the special FFT over
 the rotation group and produces NTT-form plaintexts where the kernels read them; its coefficients
 differ from encode()'s by at most a unit of rounding (tests/test_encode_cpu.py).
+
+Sparse packing, Encoder(n, slots=n_s) with n_s a power of two below N/2: the message lives in the
+subring Z[Y]/(Y^(2 n_s) + 1), Y = X^gap, gap = N / (2 n_s).  Encoding n_s values is encoding them
+tiled gap times (an n_s-periodic slot vector has no coefficient off the multiples of gap);
+decoding zeroes the coefficients off the multiples of gap first -- the projection onto the
+subring -- and returns the first n_s slots (the device path: fhe_encode_sparse / fhe_decode_sparse).
 """
 from __future__ import annotations
 
@@ -22,23 +28,26 @@ import numpy as np
 
 
 class Encoder:
-    def __init__(self, n: int):
+    def __init__(self, n: int, slots: int | None = None):
         self.n = n
-        self.slots = n // 2
+        self.slots = n // 2 if slots is None else int(slots)
+        if self.slots < 1 or self.slots & (self.slots - 1) or self.slots > n // 2:
+            raise ValueError(f"Encoder: slots must be a power of two in [1, {n // 2}]")
+        self.gap = n // (2 * self.slots)
         two_n = 2 * n
-        self.pos = np.empty(self.slots, dtype=np.int64)  # 5^j mod 2N
+        self.pos = np.empty(n // 2, dtype=np.int64)  # 5^j mod 2N
         e = 1
-        for j in range(self.slots):
+        for j in range(n // 2):
             self.pos[j] = e
             e = e * 5 % two_n
 
     def encode(self, z, delta: float) -> np.ndarray:
-        """z: complex [N/2] -> int64 coefficients [N] (|delta m| must stay below 2^62)."""
+        """z: complex [slots] -> int64 coefficients [N] (|delta m| must stay below 2^62)."""
         z = np.asarray(z, dtype=np.complex128)
         if z.shape != (self.slots,):
             raise ValueError(f"encode: expected {self.slots} slots")
         a = np.zeros(2 * self.n, dtype=np.complex128)
-        a[self.pos] = z
+        a[self.pos] = np.tile(z, self.gap)
         m = (2.0 / self.n) * np.fft.fft(a)[: self.n].real
         c = np.rint(m * delta)
         if np.abs(c).max(initial=0) >= 2.0 ** 62:
@@ -46,10 +55,11 @@ class Encoder:
         return c.astype(np.int64)
 
     def decode(self, coeffs, delta: float) -> np.ndarray:
-        """Signed integer coefficients [N] (ints or floats) -> complex slots [N/2]."""
+        """Signed integer coefficients [N] (ints or floats) -> complex slots [slots]; below full
+        packing only the coefficients at the multiples of gap count."""
         b = np.zeros(2 * self.n, dtype=np.complex128)
-        b[: self.n] = np.asarray(coeffs, dtype=np.float64)
-        return (2 * self.n) * np.fft.ifft(b)[self.pos] / delta
+        b[: self.n: self.gap] = np.asarray(coeffs, dtype=np.float64)[:: self.gap]
+        return (2 * self.n) * np.fft.ifft(b)[self.pos[: self.slots]] / delta
 
 
 def to_rns(coeffs, moduli) -> np.ndarray:

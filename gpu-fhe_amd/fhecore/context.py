@@ -845,16 +845,26 @@ class Context:
         return out
 
     # ---- CKKS encode / decode on the device (fhe_encode / fhe_decode) -----------------------
-    def _slots(self, z, who):
+    def _log_slots(self, log_slots, who):
+        """(log_slots or log_n - 1, the slot count); sparse packing is 0 <= log_slots < log_n - 1."""
+        if log_slots is None:
+            return self.log_n - 1, self.n // 2
+        if not 0 <= int(log_slots) <= self.log_n - 1:
+            raise ValueError(f"{who}: log_slots must be in [0, {self.log_n - 1}]")
+        return int(log_slots), 1 << int(log_slots)
+
+    def _slots(self, z, who, ns=None):
+        ns = self.n // 2 if ns is None else ns
         if not isinstance(z, torch.Tensor):
             z = torch.from_numpy(np.ascontiguousarray(np.asarray(z, dtype=np.complex128)))
         if z.dtype != torch.complex128:
             raise TypeError(f"{who}: expected complex128 slots, got {z.dtype}")
-        if z.shape[-1] != self.n // 2:
-            raise ValueError(f"{who}: expected [..., {self.n // 2}] slots, got {tuple(z.shape)}")
+        if z.dim() < 1 or z.shape[-1] != ns:
+            raise ValueError(f"{who}: expected [..., {ns}] slots, got {tuple(z.shape)}")
         return z.to(self._dev()).contiguous()
 
-    def encode(self, z, delta, level=None, special=False, workspace=None, out=None):
+    def encode(self, z, delta, level=None, special=False, workspace=None, out=None,
+               log_slots=None):
         """z complex128 [..., N/2] (a host array is moved to the device first) -> the plaintexts
         [..., level (+ K), N] in NTT form (fhe_encode): the inverse special FFT over the rotation
         group, c = rint(v delta / (N/2)), every row the NTT of c modulo its limb -- the Q-limbs
@@ -863,35 +873,51 @@ class Context:
         special=False is the [level, N] plaintext of mul_plain / encrypt.  Slot j sits at the root
         exp(i pi 5^j / N) as in fhecore.ckks.Encoder, whose coefficients this differs from by at
         most a unit.  Precondition: |c| < 2^62.  workspace: fhe_encode_workspace(ctx, count) bytes;
-        None takes the context's internal one, which is refused while a Graph is capturing."""
-        z = self._slots(z, "encode")
+        None takes the context's internal one, which is refused while a Graph is capturing.
+
+        log_slots (sparse packing, fhe_encode_sparse): z is [..., 2^log_slots] and the result is,
+        bit for bit, the encoding of z tiled N / 2^(log_slots + 1) times: the plaintext of
+        Z[Y]/(Y^(2 n_s) + 1), Y = X^gap, with zeros between the multiples of gap.  None is full
+        packing (fhe_encode)."""
+        ls, ns = self._log_slots(log_slots, "encode")
+        z = self._slots(z, "encode", ns)
         level = self.L if level is None else int(level)  # range-checked by fhe_encode
         rows = level + (self.K if special else 0)
-        count = z.numel() // (self.n // 2)
+        count = z.numel() // ns
         shape = (*z.shape[:-1], rows, self.n)
         if out is None:
             out = _empty(shape, dtype=torch.int64, device=z.device)
         else:
             _check_out(out, z, shape, "encode: out")
         with torch.cuda.device(self.device):
-            check(load().fhe_encode(self._ptr, _ptr(out), _ptr(z), float(delta), level,
-                                    int(bool(special)), count, _ptr(workspace), _stream(z)),
-                  "fhe_encode")
+            if log_slots is None:
+                check(load().fhe_encode(self._ptr, _ptr(out), _ptr(z), float(delta), level,
+                                        int(bool(special)), count, _ptr(workspace), _stream(z)),
+                      "fhe_encode")
+            else:
+                check(load().fhe_encode_sparse(self._ptr, _ptr(out), _ptr(z), float(delta), ls,
+                                               level, int(bool(special)), count, _ptr(workspace),
+                                               _stream(z)), "fhe_encode_sparse")
         return out
 
-    def decode(self, pt, delta, level=None, workspace=None, out=None):
+    def decode(self, pt, delta, level=None, workspace=None, out=None, log_slots=None):
         """pt [..., rows, N] NTT form -> complex128 slots [..., N/2] (fhe_decode).  level (default:
         min(rows, L)) says how many Q-limbs pt carries a value over; limb 0 is read, and limb 1 at
         level >= 2, through the rows' own stride (an [L + K, N] diagonal decodes in place).  The
         value is centred over q_0 q_1 (q_0 at level 1), so the plaintext's true centred value must
-        be below q_0 q_1 / 2 (q_0 / 2) in magnitude."""
+        be below q_0 q_1 / 2 (q_0 / 2) in magnitude.
+
+        log_slots (sparse packing, fhe_decode_sparse): only the coefficients at the multiples of
+        gap = N / 2^(log_slots + 1) are read -- the projection onto the subring, which drops what
+        a ciphertext's noise left between them -- and the result is [..., 2^log_slots]."""
+        ls, ns = self._log_slots(log_slots, "decode")
         _check_tensor(pt, "decode: pt")
         if pt.dim() < 2 or pt.shape[-1] != self.n:
             raise ValueError(f"decode: expected [..., rows, {self.n}], got {tuple(pt.shape)}")
         rows = pt.shape[-2]
         level = min(rows, self.L) if level is None else int(level)  # range-checked by fhe_decode
         count = pt.numel() // (rows * self.n)
-        shape = (*pt.shape[:-2], self.n // 2)
+        shape = (*pt.shape[:-2], ns)
         if out is None:
             out = _empty(shape, dtype=torch.complex128, device=pt.device)
         else:
@@ -901,11 +927,16 @@ class Context:
                 raise ValueError(f"decode: out must be a contiguous complex128 {shape} tensor on "
                                  "pt's device")
         with torch.cuda.device(self.device):
-            check(load().fhe_decode(self._ptr, _ptr(out), _ptr(pt), float(delta), rows, level,
-                                    count, _ptr(workspace), _stream(pt)), "fhe_decode")
+            if log_slots is None:
+                check(load().fhe_decode(self._ptr, _ptr(out), _ptr(pt), float(delta), rows, level,
+                                        count, _ptr(workspace), _stream(pt)), "fhe_decode")
+            else:
+                check(load().fhe_decode_sparse(self._ptr, _ptr(out), _ptr(pt), float(delta), ls,
+                                               rows, level, count, _ptr(workspace), _stream(pt)),
+                      "fhe_decode_sparse")
         return out
 
-    def encode_diagonals(self, diags, n1: int, n2: int, delta, level=None):
+    def encode_diagonals(self, diags, n1: int, n2: int, delta, level=None, log_slots=None):
         """The plaintexts of a baby-step / giant-step matrix product from a slot matrix's
         diagonals: diags maps k < n1 n2 to the complex [N/2] vector d_k[j] = A[j][(j + k) mod N/2]
         (absent diagonals are zero).  Returns (baby_elts, giant_elts, pts) for linear_transform,
@@ -916,20 +947,22 @@ class Context:
         A z = sum_g rot_{g n1}(sum_b rot_{-g n1}(d_k) * rot_b(z)), so pts[g][b] encodes d_k rolled
         towards higher indices by g n1 (torch.roll(d_k, g n1)), over Q u P at scale delta.  All
         n1 n2 encodings are one fhe_encode call.  level is accepted for symmetry with the other
-        calls: the plaintexts are the top-level [L + K, N] ones, read in place at every level."""
+        calls: the plaintexts are the top-level [L + K, N] ones, read in place at every level.
+        log_slots: the diagonals are [2^log_slots] vectors of a sparsely packed matrix (encode's
+        keyword); the rotation steps are taken on the full ring all the same."""
         if n1 < 1 or n2 < 1:
             raise ValueError("encode_diagonals: n1, n2 >= 1")
         if level is not None and not 1 <= int(level) <= self.L:
             raise ValueError("encode_diagonals: level must be in [1, L]")
-        ns = self.n // 2
+        _, ns = self._log_slots(log_slots, "encode_diagonals")
         bad = [k for k in diags if not 0 <= int(k) < n1 * n2]
         if bad:
             raise ValueError(f"encode_diagonals: diagonal indices {bad} outside [0, n1 n2)")
         z = torch.zeros(n2, n1, ns, dtype=torch.complex128, device=self._dev())
         for k, d in diags.items():
             g, b = divmod(int(k), n1)
-            z[g, b] = torch.roll(self._slots(d, "encode_diagonals").reshape(ns), g * n1)
-        enc = self.encode(z, delta, level=self.L, special=True)
+            z[g, b] = torch.roll(self._slots(d, "encode_diagonals", ns).reshape(ns), g * n1)
+        enc = self.encode(z, delta, level=self.L, special=True, log_slots=log_slots)
         baby = [self.galois_elt(b) for b in range(n1)]
         giant = [self.galois_elt(g * n1) for g in range(n2)]
         return baby, giant, [[enc[g, b] for b in range(n1)] for g in range(n2)]

@@ -609,6 +609,36 @@ int fhe_decode(const fhe_ctx* ctx, double* slots, const uint64_t* pt, double del
                uint32_t pt_rows, uint32_t level, uint32_t count, void* workspace,
                fhe_stream_t stream);
 
+/* ---- Sparse packing: n_s = 2^log_slots slots, 0 <= log_slots <= log_n - 1 --------------------
+ * With gap = N / (2 n_s) and Y = X^gap the message lives in the subring Z[Y]/(Y^(2 n_s) + 1): a
+ * sparse plaintext is an ordinary plaintext whose slot vector is n_s-periodic, and every other
+ * call (encrypt, rotate, multiply, the linear transform) takes it as it is.  The subring's tables
+ * are slices of the context's own: W_s[k] = W[k gap], 5^j mod 4 n_s = rot[j] mod 4 n_s.
+ *
+ * fhe_encode_sparse: slots is [count][n_s][2] doubles; out is fhe_encode's [count][level (+ K)][N].
+ *   v = z;  for len = n_s, n_s/2 .. 2 (lh = len/2, lq = 4 len):
+ *       w = W[(lq - rot[j] % lq) (M/lq)];  (a, b) -> (a + b, (a - b) w)       (M = 2N, as above)
+ *   v = v[bitrev over log_slots bits];  s = delta / n_s;
+ *   c[k gap] = rint(Re v[k] s),  c[(k + n_s) gap] = rint(Im v[k] s),  every other coefficient 0;
+ *   the rows are fhe_encode's.  The result equals fhe_encode of the vector tiled gap times bit for
+ *   bit: the first log2(gap) stages of the tiled transform only double, and delta / n against
+ *   delta / n_s is a power of two.
+ * fhe_decode_sparse: INTT and centring as fhe_decode, of the coefficients k gap only (the
+ *   projection onto the subring: what a ciphertext's noise leaves between them is not read);
+ *   x'[k] = x[k gap], k < 2 n_s;  v[k] = (x'[k], x'[k + n_s]);  v = v[bitrev];  the stages
+ *   len = 2 .. n_s with w = W[(rot[j] % lq) (M/lq)];  slots [count][n_s][2] = v / delta.
+ * log_slots = log_n - 1 is fhe_encode / fhe_decode (the same launches); log_slots = 0 is one slot
+ * with no stage, c[0] and c[N/2].  Every refusal of the full calls carries over, the overlap
+ * checks with the sparse slot extent; log_slots > log_n - 1 is FHE_EINVAL before any launch.
+ * Workspace: fhe_encode_workspace / fhe_decode_workspace(ctx, count) bytes; capture-safe with an
+ * explicit one.  FHECORE_ENCODE_UNFUSED=1 is honoured. */
+int fhe_encode_sparse(const fhe_ctx* ctx, uint64_t* out, const double* slots, double delta,
+                      uint32_t log_slots, uint32_t level, int special, uint32_t count,
+                      void* workspace, fhe_stream_t stream);
+int fhe_decode_sparse(const fhe_ctx* ctx, double* slots, const uint64_t* pt, double delta,
+                      uint32_t log_slots, uint32_t pt_rows, uint32_t level, uint32_t count,
+                      void* workspace, fhe_stream_t stream);
+
 /* ---- HIP graphs: capture a sequence of libfhecore calls on `stream` and replay it -----------
  * Between fhe_graph_begin and fhe_graph_end every call that takes a workspace must be given an
  * explicit one: with workspace == NULL a call returns FHE_EINVAL while the stream is capturing

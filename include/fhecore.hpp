@@ -554,6 +554,40 @@ class Evaluator {
           "fhe_decode");
     return out;
   }
+  // Sparse packing (fhe_encode_sparse): slots holds 2^log_slots complex doubles (2^(log_slots + 1)
+  // words).  The result is the plaintext of the vector tiled N / 2^(log_slots + 1) times, bit for
+  // bit; every other call takes it like any plaintext.
+  Ciphertext encode(const DeviceBuffer& slots, double delta, uint32_t log_slots, uint32_t level,
+                    bool special) const {
+    if (log_slots > ctx_.log_n() - 1)
+      throw Error(FHE_EINVAL, "encode: log_slots must be in [0, log_n - 1]");
+    if (slots.size() != (size_t)2 << log_slots)
+      throw Error(FHE_EINVAL, "encode: need 2^log_slots complex slots (2^(log_slots + 1) words)");
+    if (level == 0 || level > ctx_.L())
+      throw Error(FHE_EINVAL, "encode: level must be in [1, L]");
+    Ciphertext out(ctx_, 1, level + (special ? ctx_.K() : 0), true);
+    const size_t need = fhe_encode_workspace(ctx_.get(), 1);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    check(fhe_encode_sparse(ctx_.get(), out.data(), reinterpret_cast<const double*>(slots.data()),
+                            delta, log_slots, level, special ? 1 : 0, 1, ws_.data(), s_),
+          "fhe_encode_sparse");
+    return out;
+  }
+  // Sparse decode (fhe_decode_sparse): the coefficients at the multiples of N / 2^(log_slots + 1)
+  // only -> 2^log_slots complex doubles in a buffer of 2^(log_slots + 1) words.
+  DeviceBuffer decode(const Ciphertext& pt, double delta, uint32_t log_slots, uint32_t level) const {
+    if (pt.components != 1 || !pt.ntt_form)
+      throw Error(FHE_EINVAL, "decode: need a 1-component NTT-form plaintext");
+    if (log_slots > ctx_.log_n() - 1)
+      throw Error(FHE_EINVAL, "decode: log_slots must be in [0, log_n - 1]");
+    DeviceBuffer out((size_t)2 << log_slots);
+    const size_t need = fhe_decode_workspace(ctx_.get(), 1);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    check(fhe_decode_sparse(ctx_.get(), reinterpret_cast<double*>(out.data()), pt.data(), delta,
+                            log_slots, pt.limbs, level, 1, ws_.data(), s_),
+          "fhe_decode_sparse");
+    return out;
+  }
 
  private:
   uint64_t* plain_ws() const {

@@ -12,9 +12,14 @@ at level 9 -- under device keys with a secret of Hamming weight 28, in one proce
     the fused one first; the two are timed back to back, `--rounds` times alternating, and the
     median and the ratio are reported as measured.
 
+With `--log-slots A B ..` the sparse bootstraps at 2^A, 2^B .. slots (BootstrapParams.log_slots)
+run interleaved with the full-packing one, iteration by iteration, in the same process, under the
+same secret; one record each, with the phase `subsum` and the slot error, and the split / merge
+comparison is left out.
+
 One JSON line per record.
 
-  python tools/bootstrap_times.py [--steps 5] [--warmup 2] [--out FILE]"""
+  python tools/bootstrap_times.py [--steps 5] [--warmup 2] [--log-slots 10 12] [--out FILE]"""
 import argparse
 import json
 import os
@@ -30,7 +35,7 @@ import fhecore as fc  # noqa: E402
 from fhecore import bootstrap as bs  # noqa: E402
 from fhecore.polyeval import Ct  # noqa: E402
 
-PHASES = ("mod_raise", "coeff_to_slot", "split", "eval_mod", "merge", "slot_to_coeff")
+PHASES = ("mod_raise", "subsum", "coeff_to_slot", "split", "eval_mod", "merge", "slot_to_coeff")
 
 
 def timed_ms(fn, steps, warmup):
@@ -67,6 +72,8 @@ def main():
     ap.add_argument("--L", type=int, default=24)
     ap.add_argument("--K", type=int, default=6, help="special primes")
     ap.add_argument("--dnum", type=int, default=4)
+    ap.add_argument("--log-slots", type=int, nargs="*", default=None,
+                    help="also run the sparse bootstraps at these slot counts, interleaved")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -86,42 +93,59 @@ def main():
             sink.write(line + "\n")
             sink.flush()
 
-    # ---- the bootstrap, phase by phase
-    params = bs.BootstrapParams()
-    sk = ctx.keygen_secret(seed=1, hamming_weight=params.hamming_weight)
-    be = bs.GpuBackend(ctx, sk=sk, seed=100)
-    boot = bs.Bootstrapper(be, params)
+    # ---- the bootstrap, phase by phase: full packing, then every --log-slots, interleaved
+    hw = bs.BootstrapParams().hamming_weight
+    sk = ctx.keygen_secret(seed=1, hamming_weight=hw)
     g = np.random.default_rng(2)
-    z = g.uniform(-1, 1, n // 2) + 1j * g.uniform(-1, 1, n // 2)
-    ct = ctx.drop_level(ctx.encrypt_sk(ctx.encode(z, delta), sk, seed=3), 1)
-    times = {p: [] for p in PHASES}
-    out = None
+    runs = []
+    for ls in [None] + list(args.log_slots or []):
+        params = bs.BootstrapParams(log_slots=ls)
+        be = bs.GpuBackend(ctx, sk=sk, seed=100)
+        boot = bs.Bootstrapper(be, params)
+        ns = n // 2 if ls is None else 1 << ls
+        z = g.uniform(-1, 1, ns) + 1j * g.uniform(-1, 1, ns)
+        ct = ctx.drop_level(ctx.encrypt_sk(ctx.encode(z, delta, log_slots=ls), sk, seed=3), 1)
+        runs.append(dict(ls=ls, params=params, be=be, boot=boot, z=z, ct=ct, out=None,
+                         times={p: [] for p in PHASES}))
     for it in range(args.warmup + args.steps):
-        ev = [torch.cuda.Event(enable_timing=True)]
-        ev[0].record()
+        for r in runs:
+            ev, names = [torch.cuda.Event(enable_timing=True)], []
+            ev[0].record()
 
-        def mark(name):
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            ev.append(e)
+            def mark(name):
+                e = torch.cuda.Event(enable_timing=True)
+                e.record()
+                ev.append(e)
+                names.append(name)
 
-        out = boot.bootstrap(Ct(ct, 1, delta), mark=mark)
-        torch.cuda.synchronize()
-        if it >= args.warmup:
-            for p, a, b in zip(PHASES, ev, ev[1:]):
-                times[p].append(a.elapsed_time(b))
-    got = ctx.decode(ctx.decrypt(out.data, sk), float(out.scale)).cpu().numpy()
-    med = {p: statistics.median(v) for p, v in times.items()}
-    emit({"op": "bootstrap", "log_n": log_n, "L": L, "special": K, "dnum": dnum,
-          "K": params.K, "degree": params.degree, "double_angles": params.double_angles,
-          "cts_groups": params.cts_groups, "stc_groups": params.stc_groups,
-          "hamming_weight": params.hamming_weight, "q0_bits": ctx.moduli[0].bit_length(),
-          "out_level": out.level, "rotation_keys": len(be.rot_keys),
-          "phase_ms": {p: round(v, 3) for p, v in med.items()},
-          "total_ms": round(sum(med.values()), 3),
-          "max_slot_error": float(np.abs(got - z).max())})
-    del boot, be, out
+            r["out"] = r["boot"].bootstrap(Ct(r["ct"], 1, delta), mark=mark)
+            torch.cuda.synchronize()
+            if it >= args.warmup:
+                for p, a, b in zip(names, ev, ev[1:]):
+                    r["times"][p].append(a.elapsed_time(b))
+    full_total = None
+    for r in runs:
+        params, out, ls = r["params"], r["out"], r["ls"]
+        got = ctx.decode(ctx.decrypt(out.data, sk), float(out.scale), log_slots=ls).cpu().numpy()
+        med = {p: statistics.median(v) for p, v in r["times"].items() if v}
+        total = sum(med.values())
+        full_total = total if ls is None else full_total
+        rec = {"op": "bootstrap", "log_n": log_n, "L": L, "special": K, "dnum": dnum,
+               "K": params.K, "degree": params.degree, "double_angles": params.double_angles,
+               "cts_groups": params.cts_groups, "stc_groups": params.stc_groups,
+               "hamming_weight": params.hamming_weight, "q0_bits": ctx.moduli[0].bit_length(),
+               "out_level": out.level, "rotation_keys": len(r["be"].rot_keys),
+               "phase_ms": {p: round(v, 3) for p, v in med.items()},
+               "total_ms": round(total, 3),
+               "max_slot_error": float(np.abs(got - r["z"]).max())}
+        if ls is not None:
+            rec.update(log_slots=ls, total_over_full_packing=round(total / full_total, 3))
+        emit(rec)
+    params = runs[0]["params"]
+    del runs
     torch.cuda.empty_cache()
+    if args.log_slots:
+        return
 
     # ---- split / merge against their composed forms
     level = L - params.cts_groups

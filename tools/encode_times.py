@@ -23,7 +23,16 @@ count (8N + 8N rows) for encode, count (8N limbs read + 8N) for decode -- over i
 fraction of the 8 TB/s HBM peak, and the special FFT's share of the call from the library's own
 per-launch events (fhe_prof_begin / fhe_prof_end).
 
-  python tools/encode_times.py [--steps 50] [--warmup 20] [--out FILE]"""
+With `--log-slots A B ..` the sparse calls are timed instead (fhe_encode_sparse /
+fhe_decode_sparse at 2^A, 2^B .. slots): encode at level L with the P rows and decode at level 2,
+each against today's only other route, fhe_encode of the vector tiled N / 2^(log_slots + 1) times
+(fhe_decode of the whole plaintext).  Per round the tiled call is timed before and after the
+sparse one; the record holds the median of either position, their difference (`tiled_spread_ms`:
+what two medians of one call differ by in this run), the sparse median, and `within_spread`:
+whether sparse - tiled <= that spread.  The tiled call is fhe_encode itself, so its time next to
+the first record above is the full path's before and after.
+
+  python tools/encode_times.py [--steps 50] [--warmup 20] [--log-slots 8 10 12 14] [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -112,6 +121,68 @@ def fft_share(fn, reps=10):
     return (fft / total if total else 0.0), {k: round(v, 4) for k, v in per.items()}
 
 
+def sparse_cases(args, ctx, emit):
+    """fhe_encode_sparse / fhe_decode_sparse against the tiled full calls, --log-slots each."""
+    lib = fc.load()
+    log_n, L, K, B = args.log_n, ctx.L, ctx.K, args.count
+    n, delta = 1 << log_n, 2.0 ** 50
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(41)
+    ews = ctx.workspace(lib.fhe_encode_workspace(ctx.handle, B))
+    dws = ctx.workspace(lib.fhe_decode_workspace(ctx.handle, B))
+    out = torch.empty(B, L + K, n, dtype=torch.int64, device="cuda")
+    for ls in args.log_slots:
+        ns, gap = 1 << ls, n // (2 << ls)
+        z = torch.view_as_complex(torch.rand(B, ns, 2, generator=gen, device="cuda",
+                                             dtype=torch.float64) * 2 - 1)
+        zt = z.repeat(1, gap).contiguous()
+        zo = torch.empty(B, ns, dtype=torch.complex128, device="cuda")
+        zf = torch.empty(B, n // 2, dtype=torch.complex128, device="cuda")
+
+        def enc_sparse():
+            ctx.encode(z, delta, special=True, workspace=ews, out=out, log_slots=ls)
+
+        def enc_tiled():
+            ctx.encode(zt, delta, special=True, workspace=ews, out=out)
+
+        def dec_sparse():
+            ctx.decode(pt, delta, level=2, workspace=dws, out=zo, log_slots=ls)
+
+        def dec_tiled():
+            ctx.decode(pt, delta, level=2, workspace=dws, out=zf)
+
+        enc_tiled()
+        pt = out.clone()
+        out.zero_()
+        enc_sparse()
+        torch.cuda.synchronize()
+        assert torch.equal(out, pt), "the sparse encode differs from the tiled one"
+        dec_sparse()
+        dec_tiled()
+        torch.cuda.synchronize()
+        assert torch.equal(zo.view(torch.float64), zf[:, :ns].contiguous().view(torch.float64)), \
+            "the sparse decode differs from the full one on an exactly sparse plaintext"
+        for op, sparse, tiled in (("encode", enc_sparse, enc_tiled), ("decode", dec_sparse, dec_tiled)):
+            a, m, b = [], [], []
+            for _ in range(args.rounds):
+                a.append(timed_ms(tiled, args.steps, args.warmup))
+                m.append(timed_ms(sparse, args.steps, args.warmup))
+                b.append(timed_ms(tiled, args.steps, args.warmup))
+            ma, mm, mb = (statistics.median(v) for v in (a, m, b))
+            mt = statistics.median(a + b)
+            _, marks = fft_share(sparse)
+            _, tmarks = fft_share(tiled)
+            emit({"op": op + "_sparse", "log_slots": ls, "log_n": log_n, "count": B,
+                  "level": L if op == "encode" else 2, "rows": L + K,
+                  "sparse_ms": round(mm, 4), "tiled_ms": round(mt, 4),
+                  "tiled_before_ms": round(ma, 4), "tiled_after_ms": round(mb, 4),
+                  "tiled_spread_ms": round(abs(ma - mb), 4),
+                  "sparse_over_tiled": round(mm / mt, 3),
+                  "within_spread": bool(mm - mt <= abs(ma - mb)),
+                  "marks_ms": marks, "tiled_marks_ms": tmarks})
+        del pt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
@@ -119,6 +190,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--count", type=int, default=32)
     ap.add_argument("--log-n", type=int, default=16)
+    ap.add_argument("--log-slots", type=int, nargs="*", default=None,
+                    help="time the sparse calls at these slot counts instead")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -145,6 +218,10 @@ def main():
         if sink:
             sink.write(line + "\n")
             sink.flush()
+
+    if args.log_slots:
+        sparse_cases(args, ctx, emit)
+        return
 
     for level, special in ((L, True), (4, False)):
         rows = level + (K if special else 0)
