@@ -295,9 +295,14 @@ int fhe_keyswitch_shard(const fhe_ctx* c, uint64_t* ks0, uint64_t* ks1, const ui
                                 evk_a, limb0, nlimbs, batch, ws, hs(s));
 }
 
-// level in [1, L] for the *_level entry points (a null context fails in check_window first)
+// The prologue of the *_level entry points: a context, and a level in [1, L] (so the limb window
+// [0, level) lies inside the chain).
 static int check_level(const fhe_ctx* c, uint32_t level, const char* who) {
-  if (c && (level == 0 || level > c->L)) {
+  if (!c) {
+    set_error(std::string(who) + ": null context");
+    return kInvalid;
+  }
+  if (level == 0 || level > c->L) {
     set_error(std::string(who) + ": level must be in [1, L]");
     return kInvalid;
   }
@@ -316,7 +321,7 @@ int fhe_keyswitch_level(const fhe_ctx* c, uint64_t* ks0, uint64_t* ks1, const ui
                         const uint64_t* evk_b, const uint64_t* evk_a, uint32_t level,
                         uint32_t batch, void* ws, fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_keyswitch_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_keyswitch_level"))) return rc;
+  if (rc) return rc;
   if (batch == 0) return kOk;
   const uint64_t ct_words = (uint64_t)level * c->n;
   // the whole batch at once: a pass must not overwrite a later pass's d2 (per-pass checks in the
@@ -384,7 +389,7 @@ int fhe_rotate_level(const fhe_ctx* c, uint64_t* out, const uint64_t* in, uint32
                      const uint64_t* rot_b, const uint64_t* rot_a, uint32_t level, uint32_t batch,
                      void* ws, fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_rotate_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_rotate_level"))) return rc;
+  if (rc) return rc;
   // the finish reads c0 through sigma (any word of its row block) while other workgroups write
   // out: any overlap of the two [batch][2][level][N] spans races, not just out == in
   const uint64_t span = (uint64_t)batch * 2 * level * c->n;
@@ -414,7 +419,7 @@ int fhe_rotate_hoisted_level(const fhe_ctx* c, uint64_t* out, const uint64_t* in
                              const uint64_t* const* rot_a, uint32_t level, uint32_t count,
                              uint32_t batch, void* ws, fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_rotate_hoisted_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_rotate_hoisted_level"))) return rc;
+  if (rc) return rc;
   if (count && (!galois_elts || !rot_b || !rot_a)) {
     set_error("fhe_rotate_hoisted: null Galois element or key array");
     return kInvalid;
@@ -454,8 +459,7 @@ int fhe_rotate_sum_hoisted_level(const fhe_ctx* c, uint64_t* out, const uint64_t
                                  uint32_t level, uint32_t count, uint32_t batch, void* ws,
                                  fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_rotate_sum_hoisted_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_rotate_sum_hoisted_level")))
-    return rc;
+  if (rc) return rc;
   if (count == 0 || count > kRotSumMax) {
     set_error("fhe_rotate_sum_hoisted: count must be 1..16");
     return kInvalid;
@@ -502,8 +506,7 @@ int fhe_rotate_sum_multi_level(const fhe_ctx* c, uint64_t* out, const uint64_t* 
                                const uint64_t* const* rot_a, uint32_t level, uint32_t count,
                                uint32_t batch, void* ws, fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_rotate_sum_multi_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_rotate_sum_multi_level")))
-    return rc;
+  if (rc) return rc;
   if (count == 0 || count > kRotSumMax) {
     set_error("fhe_rotate_sum_multi: count must be 1..16");
     return kInvalid;
@@ -553,8 +556,7 @@ int fhe_linear_transform_level(const fhe_ctx* c, uint64_t* out, const uint64_t* 
                                const uint64_t* const* giant_a, const uint64_t* const* pt,
                                uint32_t level, uint32_t batch, void* ws, fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_linear_transform_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_linear_transform_level")))
-    return rc;
+  if (rc) return rc;
   if (n1 == 0 || n1 > kRotSumMax || n2 == 0 || n2 > kRotSumMax) {
     set_error("fhe_linear_transform: n1 and n2 must be 1..16");
     return kInvalid;
@@ -603,7 +605,7 @@ int fhe_mul_relin_level(const fhe_ctx* c, uint64_t* out, const uint64_t* a, cons
                         const uint64_t* evk_b, const uint64_t* evk_a, uint32_t level,
                         uint32_t batch, int rescale, void* ws, fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_mul_relin_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_mul_relin_level"))) return rc;
+  if (rc) return rc;
   if (rescale && level < 2) {
     set_error("fhe_mul_relin_level: rescale needs level >= 2");
     return kInvalid;
@@ -634,7 +636,7 @@ int fhe_lincomb_level(const fhe_ctx* c, uint64_t* out, const uint64_t* const* ct
                       int has_const, uint32_t level, uint32_t count, uint32_t batch, int rescale,
                       void* ws, fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_lincomb_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_lincomb_level"))) return rc;
+  if (rc) return rc;
   if (count == 0 || count > kLincombMax) {
     set_error("fhe_lincomb_level: count must be 1..16");
     return kInvalid;
@@ -676,7 +678,7 @@ int fhe_mul_plain_level(const fhe_ctx* c, uint64_t* out, const uint64_t* ct, con
                         uint32_t pt_rows, uint32_t pt_batch, uint32_t level, uint32_t batch,
                         int rescale, void* ws, fhe_stream_t s) {
   int rc = check_level(c, level, "fhe_mul_plain_level");
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, "fhe_mul_plain_level"))) return rc;
+  if (rc) return rc;
   if (rescale && level < 2) {
     set_error("fhe_mul_plain_level: rescale needs level >= 2");
     return kInvalid;
@@ -710,7 +712,7 @@ int fhe_mul_plain_level(const fhe_ctx* c, uint64_t* out, const uint64_t* ct, con
 static int conj_check(const fhe_ctx* c, uint64_t* const* outs, int nout, const uint64_t* const* ins,
                       uint32_t level, uint32_t batch, const char* who) {
   int rc = check_level(c, level, who);
-  if (rc || (rc = check_window(c, 0, level, c ? c->L : 0, who))) return rc;
+  if (rc) return rc;
   for (int i = 0; i < nout; ++i)
     if (!outs[i]) return (set_error(std::string(who) + ": null data pointer"), kInvalid);
   if (!ins[0] || !ins[1]) return (set_error(std::string(who) + ": null data pointer"), kInvalid);

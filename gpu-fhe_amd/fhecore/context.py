@@ -318,13 +318,9 @@ class Context:
             lib.fhe_keyswitch_workspace(self._ptr, self.L,
                                         lib.fhe_keyswitch_pass_batch(self._ptr, batch)))
         with torch.cuda.device(self.device):
-            if lv == self.L:
-                check(lib.fhe_keyswitch(self._ptr, _ptr(ks0), _ptr(ks1), _ptr(d2), _ptr(evk_b),
-                                        _ptr(evk_a), batch, _ptr(ws), _stream(d2)), "fhe_keyswitch")
-            else:
-                check(lib.fhe_keyswitch_level(self._ptr, _ptr(ks0), _ptr(ks1), _ptr(d2),
-                                              _ptr(evk_b), _ptr(evk_a), lv, batch, _ptr(ws),
-                                              _stream(d2)), "fhe_keyswitch_level")
+            check(lib.fhe_keyswitch_level(self._ptr, _ptr(ks0), _ptr(ks1), _ptr(d2), _ptr(evk_b),
+                                          _ptr(evk_a), lv, batch, _ptr(ws), _stream(d2)),
+                  "fhe_keyswitch_level")
         return ks0, ks1
 
     # ---- rescale and rotation -------------------------------------
@@ -379,13 +375,9 @@ class Context:
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_rotate_workspace(self._ptr, lib.fhe_keyswitch_pass_batch(self._ptr, batch)))
         with torch.cuda.device(self.device):
-            if lv == self.L:
-                check(lib.fhe_rotate(self._ptr, _ptr(out), _ptr(ct), galois_elt, _ptr(rot_b),
-                                     _ptr(rot_a), batch, _ptr(ws), _stream(ct)), "fhe_rotate")
-            else:
-                check(lib.fhe_rotate_level(self._ptr, _ptr(out), _ptr(ct), galois_elt,
-                                           _ptr(rot_b), _ptr(rot_a), lv, batch, _ptr(ws),
-                                           _stream(ct)), "fhe_rotate_level")
+            check(lib.fhe_rotate_level(self._ptr, _ptr(out), _ptr(ct), galois_elt, _ptr(rot_b),
+                                       _ptr(rot_a), lv, batch, _ptr(ws), _stream(ct)),
+                  "fhe_rotate_level")
         return out
 
     def rotate_hoisted(self, ct, galois_elts, rot_keys, workspace=None, out=None):
@@ -395,14 +387,7 @@ class Context:
         Returns [count, ..., 2, l, N]; output r decrypts to sigma_r(m)."""
         lv = self._ct_level(ct, "rotate_hoisted")
         elts = [int(g) for g in galois_elts]
-        if len(rot_keys) != len(elts):
-            raise ValueError("rotate_hoisted: one key per Galois element")
-        for kb, ka in rot_keys:
-            if tuple(kb.shape) != (self.dnum, self.L + self.K, self.n) or ka.shape != kb.shape:
-                raise ValueError("rotate_hoisted: keys must be [dnum, L + K, N]")
-            if kb.device != ct.device or ka.device != ct.device or not (
-                    kb.is_contiguous() and ka.is_contiguous()):
-                raise ValueError("rotate_hoisted: keys must be contiguous on the ct's device")
+        g_arr, b_arr, a_arr = self._rot_keys(elts, rot_keys, ct, "rotate_hoisted", keyless=False)
         batch = ct.numel() // (2 * lv * self.n)
         count = len(elts)
         if out is None:
@@ -412,18 +397,10 @@ class Context:
         lib = load()
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_rotate_hoisted_workspace(self._ptr, batch))
-        g_arr = (ctypes.c_uint32 * max(count, 1))(*elts)
-        b_arr = (ctypes.c_void_p * max(count, 1))(*[kb.data_ptr() for kb, _ in rot_keys])
-        a_arr = (ctypes.c_void_p * max(count, 1))(*[ka.data_ptr() for _, ka in rot_keys])
         with torch.cuda.device(self.device):
-            if lv == self.L:
-                check(lib.fhe_rotate_hoisted(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr, a_arr,
-                                             count, batch, _ptr(ws), _stream(ct)),
-                      "fhe_rotate_hoisted")
-            else:
-                check(lib.fhe_rotate_hoisted_level(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr,
-                                                   a_arr, lv, count, batch, _ptr(ws), _stream(ct)),
-                      "fhe_rotate_hoisted_level")
+            check(lib.fhe_rotate_hoisted_level(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr, a_arr,
+                                               lv, count, batch, _ptr(ws), _stream(ct)),
+                  "fhe_rotate_hoisted_level")
         return out
 
     def rotate_sum_hoisted(self, ct, galois_elts, rot_keys, pts, workspace=None, out=None):
@@ -435,45 +412,20 @@ class Context:
         lv = self._ct_level(ct, "rotate_sum_hoisted")
         elts = [int(g) for g in galois_elts]
         count = len(elts)
-        if len(rot_keys) != count or len(pts) != count:
-            raise ValueError("rotate_sum_hoisted: one key (or None) and one plaintext per term")
-        for g, key, pt in zip(elts, rot_keys, pts):
-            if tuple(pt.shape) != (self.L + self.K, self.n) or pt.device != ct.device or not \
-                    pt.is_contiguous():
-                raise ValueError("rotate_sum_hoisted: plaintexts must be contiguous [L + K, N] "
-                                 "on the ct's device")
-            if key is None:
-                if g != 1:
-                    raise ValueError("rotate_sum_hoisted: only Galois element 1 takes no key")
-                continue
-            kb, ka = key
-            if tuple(kb.shape) != (self.dnum, self.L + self.K, self.n) or ka.shape != kb.shape:
-                raise ValueError("rotate_sum_hoisted: keys must be [dnum, L + K, N]")
-            if kb.device != ct.device or ka.device != ct.device or not (
-                    kb.is_contiguous() and ka.is_contiguous()):
-                raise ValueError("rotate_sum_hoisted: keys must be contiguous on the ct's device")
+        if len(pts) != count:
+            raise ValueError("rotate_sum_hoisted: one plaintext per term")
+        g_arr, b_arr, a_arr = self._rot_keys(elts, rot_keys, ct, "rotate_sum_hoisted")
+        p_arr = self._pts(pts, ct, "rotate_sum_hoisted")
         batch = ct.numel() // (2 * lv * self.n)
-        if out is None:
-            out = _empty(*ct.shape, dtype=ct.dtype, device=ct.device)
-        else:
-            _check_out(out, ct, tuple(ct.shape), "rotate_sum_hoisted: out")
+        out = _empty_like(ct) if out is None else _check_out(out, ct, ct.shape,
+                                                             "rotate_sum_hoisted: out")
         lib = load()
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_rotate_sum_hoisted_workspace(self._ptr, batch))
-        n_arr = max(count, 1)
-        g_arr = (ctypes.c_uint32 * n_arr)(*elts)
-        b_arr = (ctypes.c_void_p * n_arr)(*[k[0].data_ptr() if k else None for k in rot_keys])
-        a_arr = (ctypes.c_void_p * n_arr)(*[k[1].data_ptr() if k else None for k in rot_keys])
-        p_arr = (ctypes.c_void_p * n_arr)(*[p.data_ptr() for p in pts])
         with torch.cuda.device(self.device):
-            if lv == self.L:
-                check(lib.fhe_rotate_sum_hoisted(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr,
-                                                 a_arr, p_arr, count, batch, _ptr(ws),
-                                                 _stream(ct)), "fhe_rotate_sum_hoisted")
-            else:
-                check(lib.fhe_rotate_sum_hoisted_level(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr,
-                                                       a_arr, p_arr, lv, count, batch, _ptr(ws),
-                                                       _stream(ct)), "fhe_rotate_sum_hoisted_level")
+            check(lib.fhe_rotate_sum_hoisted_level(self._ptr, _ptr(out), _ptr(ct), g_arr, b_arr,
+                                                   a_arr, p_arr, lv, count, batch, _ptr(ws),
+                                                   _stream(ct)), "fhe_rotate_sum_hoisted_level")
         return out
 
     def _ct_level(self, ct, who):
@@ -483,14 +435,16 @@ class Context:
             raise ValueError(f"{who}: ct must be [..., 2, l, N]")
         return self._level(ct, f"{who}: ct")
 
-    def _rot_keys(self, elts, rot_keys, ct, who):
-        """Host arrays of key pointers (None for the unrotated element 1), shapes checked."""
+    def _rot_keys(self, elts, rot_keys, ct, who, keyless=True):
+        """Host arrays of Galois elements and key pointers, shapes checked.  keyless: the
+        unrotated element 1 takes None for a key (rotate_hoisted needs one for every element)."""
         if len(rot_keys) != len(elts):
-            raise ValueError(f"{who}: one key (or None) per Galois element")
+            raise ValueError(f"{who}: one key{' (or None)' if keyless else ''} per Galois element")
         for g, key in zip(elts, rot_keys):
             if key is None:
-                if g != 1:
-                    raise ValueError(f"{who}: only Galois element 1 takes no key")
+                if g != 1 or not keyless:
+                    raise ValueError(f"{who}: only Galois element 1 takes no key" if keyless else
+                                     f"{who}: every Galois element takes a key")
                 continue
             kb, ka = key
             if tuple(kb.shape) != (self.dnum, self.L + self.K, self.n) or ka.shape != kb.shape:
@@ -528,23 +482,16 @@ class Context:
             raise ValueError("rotate_sum_multi: one Galois element per ciphertext")
         g_arr, b_arr, a_arr = self._rot_keys(elts, rot_keys, ct, "rotate_sum_multi")
         batch = ct.numel() // (2 * lv * self.n)
-        if out is None:
-            out = _empty(*ct.shape, dtype=ct.dtype, device=ct.device)
-        else:
-            _check_out(out, ct, tuple(ct.shape), "rotate_sum_multi: out")
+        out = _empty_like(ct) if out is None else _check_out(out, ct, ct.shape,
+                                                             "rotate_sum_multi: out")
         lib = load()
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_rotate_sum_multi_workspace(self._ptr, len(cts), batch))
         c_arr = (ctypes.c_void_p * len(cts))(*[c.data_ptr() for c in cts])
         with torch.cuda.device(self.device):
-            if lv == self.L:
-                check(lib.fhe_rotate_sum_multi(self._ptr, _ptr(out), c_arr, g_arr, b_arr, a_arr,
-                                               len(elts), batch, _ptr(ws), _stream(ct)),
-                      "fhe_rotate_sum_multi")
-            else:
-                check(lib.fhe_rotate_sum_multi_level(self._ptr, _ptr(out), c_arr, g_arr, b_arr,
-                                                     a_arr, lv, len(elts), batch, _ptr(ws),
-                                                     _stream(ct)), "fhe_rotate_sum_multi_level")
+            check(lib.fhe_rotate_sum_multi_level(self._ptr, _ptr(out), c_arr, g_arr, b_arr, a_arr,
+                                                 lv, len(elts), batch, _ptr(ws), _stream(ct)),
+                  "fhe_rotate_sum_multi_level")
         return out
 
     def linear_transform(self, ct, baby_elts, baby_keys, giant_elts, giant_keys, pts,
@@ -564,22 +511,15 @@ class Context:
         gg, gb, ga = self._rot_keys(giant, giant_keys, ct, "linear_transform")
         p_arr = self._pts([p for row in pts for p in row], ct, "linear_transform")
         batch = ct.numel() // (2 * lv * self.n)
-        if out is None:
-            out = _empty(*ct.shape, dtype=ct.dtype, device=ct.device)
-        else:
-            _check_out(out, ct, tuple(ct.shape), "linear_transform: out")
+        out = _empty_like(ct) if out is None else _check_out(out, ct, ct.shape,
+                                                             "linear_transform: out")
         lib = load()
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_linear_transform_workspace(self._ptr, n2, batch))
         with torch.cuda.device(self.device):
-            if lv == self.L:
-                check(lib.fhe_linear_transform(self._ptr, _ptr(out), _ptr(ct), n1, n2, bg, bb, ba,
-                                               gg, gb, ga, p_arr, batch, _ptr(ws), _stream(ct)),
-                      "fhe_linear_transform")
-            else:
-                check(lib.fhe_linear_transform_level(self._ptr, _ptr(out), _ptr(ct), n1, n2, bg, bb,
-                                                     ba, gg, gb, ga, p_arr, lv, batch, _ptr(ws),
-                                                     _stream(ct)), "fhe_linear_transform_level")
+            check(lib.fhe_linear_transform_level(self._ptr, _ptr(out), _ptr(ct), n1, n2, bg, bb, ba,
+                                                 gg, gb, ga, p_arr, lv, batch, _ptr(ws),
+                                                 _stream(ct)), "fhe_linear_transform_level")
         return out
 
     # ---- sampling, keys, encryption --------------------------------
@@ -695,14 +635,9 @@ class Context:
         ws = workspace if workspace is not None else self.workspace(
             lib.fhe_mul_relin_workspace(self._ptr, lib.fhe_keyswitch_pass_batch(self._ptr, batch)))
         with torch.cuda.device(self.device):
-            if lv == self.L:
-                check(lib.fhe_mul_relin(self._ptr, _ptr(out), _ptr(a), _ptr(b), _ptr(evk_b),
-                                        _ptr(evk_a), batch, int(rescale), _ptr(ws), _stream(a)),
-                      "fhe_mul_relin")
-            else:
-                check(lib.fhe_mul_relin_level(self._ptr, _ptr(out), _ptr(a), _ptr(b), _ptr(evk_b),
-                                              _ptr(evk_a), lv, batch, int(rescale), _ptr(ws),
-                                              _stream(a)), "fhe_mul_relin_level")
+            check(lib.fhe_mul_relin_level(self._ptr, _ptr(out), _ptr(a), _ptr(b), _ptr(evk_b),
+                                          _ptr(evk_a), lv, batch, int(rescale), _ptr(ws),
+                                          _stream(a)), "fhe_mul_relin_level")
         return out
 
     # ---- plaintext arithmetic at any level (fhe_lincomb_level / fhe_mul_plain_level) --------

@@ -392,7 +392,7 @@ int fhe_linear_transform(const fhe_ctx* ctx, uint64_t* out, const uint64_t* in, 
  * read in place at those rows (a diagonal is an integer polynomial whose residues do not depend
  * on the level, so one encoding over Q u P serves every level, like a key).  Everything else is
  * the top-level definition (oracle/pyoracle.py rotate_hoisted, rotate_sum_hoisted,
- * rotate_sum_multi, linear_transform; restated for a level by tests/level_hoist_ref.py).
+ * rotate_sum_multi, linear_transform, which take the level as level=).
  * level == L is bit-identical to the top-level forms, which are these calls with level = L.
  * Errors: level == 0 or level > L returns FHE_EINVAL before any launch; every other error and
  * aliasing rule is the top-level one with l in place of L.

@@ -346,21 +346,50 @@ def baseconv(x, src, dst):
     return np.stack(out)
 
 
-def digit_ranges(L: int, dnum: int):
-    """Limb ranges of the dnum gadget digits: alpha = ceil(L / dnum) limbs each (last may be short)."""
+# Levels.  Level l (1 <= l <= L) is the top-level operation on the Q-limbs 0 .. l-1 of a chain of
+# L, with the top-level keys (dnum, L + K, N) and plaintext diagonals (L + K, N) unchanged: a key's
+# gadget factor P g_j is P mod q_i on the limbs of digit j and 0 on the other Q-limbs whatever the
+# number of live limbs, and a diagonal is an integer polynomial whose residues do not depend on the
+# level.  So level l uses
+#   * the moduli qs[:l] u ps,
+#   * digits D_j = [j alpha, min(l, (j + 1) alpha)) for j < ceil(l / alpha), alpha = ceil(L / dnum)
+#     the top-level digit width (digit_ranges),
+#   * rows {0 .. l-1} u {L .. L+K-1} of those digits' keys and of the diagonals (key_rows),
+# and everything else word for word.  Every function of the key-switch family takes level= (None:
+# L = len(qs)) and ntt=, a pair (fwd, inv) of functions (x, moduli) -> object array (None:
+# rns_ntt_fwd / rns_ntt_inv, the definition; tests pass the C restatement's for speed).
+
+def digit_ranges(L: int, dnum: int, level=None):
+    """Limb ranges of the gadget digits live at `level`: alpha = ceil(L / dnum) limbs each, the
+    last one cut at `level` (at the top: the last may be short)."""
     alpha = -(-L // dnum)
-    return [(j * alpha, min(L, (j + 1) * alpha)) for j in range(dnum) if j * alpha < L]
+    level = L if level is None else level
+    return [(lo, min(level, lo + alpha)) for lo in range(0, level, alpha)]
 
 
-def modup(c, qs, ps, dnum):
-    """c: (L, N) coefficient form over Q. Returns [dnum] arrays of shape (L + K, N): digit j
-    extended from its limbs D_j to every limb of Q u P (own limbs copied)."""
+def key_rows(level: int, L: int, K: int):
+    """Rows of a top-level key digit or plaintext diagonal (L + K, N) that level `level` reads."""
+    return list(range(level)) + list(range(L, L + K))
+
+
+def _live(qs, ps, level, ntt):
+    """(qs[:level], ps, key_rows, fwd, inv) with the defaults of level= and ntt= filled in."""
     qs = [int(q) for q in qs]
     ps = [int(p) for p in ps]
-    allm = qs + ps
+    level = len(qs) if level is None else level
+    fwd, inv = ntt or (rns_ntt_fwd, rns_ntt_inv)
+    return qs[:level], ps, key_rows(level, len(qs), len(ps)), fwd, inv
+
+
+def modup(c, qs, ps, dnum, level=None):
+    """c: (level, N) coefficient form over qs[:level]. Returns one (level + K, N) array per live
+    digit: digit j extended from its limbs D_j to every limb of qs[:level] u ps (own limbs
+    copied)."""
+    ql, ps = _live(qs, ps, level, None)[:2]
+    allm = ql + ps
     out = []
-    for lo, hi in digit_ranges(len(qs), dnum):
-        dj = qs[lo:hi]
+    for lo, hi in digit_ranges(len(qs), dnum, len(ql)):
+        dj = ql[lo:hi]
         others = [i for i in range(len(allm)) if not lo <= i < hi]
         conv = baseconv(c[lo:hi], dj, [allm[i] for i in others])
         ext = np.empty((len(allm), c.shape[-1]), dtype=object)
@@ -371,15 +400,36 @@ def modup(c, qs, ps, dnum):
     return out
 
 
-def moddown_ntt(acc, qs, ps):
-    """acc: (L + K, N) NTT form over Q u P -> (L, N) NTT form over Q:
+def modup_ntt(c1, qs, ps, dnum, level=None, ntt=None):
+    """ModUp of c1 (level, N) NTT form: INTT, digit base conversion, NTT of every extended digit.
+    The live digits, each (level + K, N) NTT form; a digit's own rows are c1 itself
+    (NTT(INTT(c1)) = c1)."""
+    ql, ps, _, fwd, inv = _live(qs, ps, level, ntt)
+    c1 = np.asarray(c1).astype(object)
+    ext = [fwd(e, ql + ps) for e in modup(inv(c1, ql), qs, ps, dnum, len(ql))]
+    for (lo, hi), e in zip(digit_ranges(len(qs), dnum, len(ql)), ext):
+        e[lo:hi] = c1[lo:hi]
+    return ext
+
+
+def _gathered_inner(ext, idx, kb, ka, rows, mods):
+    """The inner product of the live digits, gathered through idx (sigma_k in the NTT domain), with
+    the rows `rows` of the key (kb, ka): (acc0, acc1) over qs[:level] u ps."""
+    acc0 = np.zeros(ext[0].shape, dtype=object)
+    acc1 = np.zeros_like(acc0)
+    for j, e in enumerate(ext):
+        g = e[..., idx]
+        acc0 = (acc0 + g * np.asarray(kb[j])[rows].astype(object)) % mods
+        acc1 = (acc1 + g * np.asarray(ka[j])[rows].astype(object)) % mods
+    return acc0, acc1
+
+
+def moddown_ntt(acc, qs, ps, ntt=None):
+    """acc: (L + K, N) NTT form over Q u P -> (L, N) NTT form over Q (any limb list qs):
     out = (acc_Q - NTT(conv_{P->Q}(INTT(acc_P)))) * P^-1 mod q_i."""
-    qs = [int(q) for q in qs]
-    ps = [int(p) for p in ps]
+    qs, ps, _, fwd, inv = _live(qs, ps, None, ntt)
     L = len(qs)
-    xp = rns_ntt_inv(np.asarray(acc[L:]), ps)
-    conv = baseconv(xp, ps, qs)
-    convn = rns_ntt_fwd(conv, qs)
+    convn = fwd(baseconv(inv(np.asarray(acc[L:]), ps), ps, qs), qs)
     P = math.prod(ps)
     out = []
     for i, q in enumerate(qs):
@@ -387,20 +437,14 @@ def moddown_ntt(acc, qs, ps):
     return np.stack(out)
 
 
-def keyswitch(d2_ntt, evk_b, evk_a, qs, ps, dnum):
-    """Hybrid key-switch (SURVEY.md §8a'): d2 (L, N) NTT form over Q; evk_b/evk_a (dnum, L+K, N)
-    NTT form over Q u P.  Returns (ks0, ks1), each (L, N) NTT form over Q."""
-    allm = list(qs) + list(ps)
-    c = rns_ntt_inv(d2_ntt, qs)
-    ext = modup(c, qs, ps, dnum)
-    mods = _mods_col(allm)
-    acc0 = np.zeros((len(allm), c.shape[-1]), dtype=object)
-    acc1 = np.zeros_like(acc0)
-    for j, e in enumerate(ext):
-        en = rns_ntt_fwd(e, allm)
-        acc0 = (acc0 + en * np.asarray(evk_b[j]).astype(object)) % mods
-        acc1 = (acc1 + en * np.asarray(evk_a[j]).astype(object)) % mods
-    return moddown_ntt(acc0, qs, ps), moddown_ntt(acc1, qs, ps)
+def keyswitch(d2_ntt, evk_b, evk_a, qs, ps, dnum, *, level=None, ntt=None):
+    """Hybrid key-switch (SURVEY.md §8a'): d2 (level, N) NTT form over qs[:level]; evk_b/evk_a
+    (dnum, L+K, N) NTT form over Q u P, the top-level key.  Returns (ks0, ks1), each (level, N) NTT
+    form over qs[:level]."""
+    ql, ps, rows, _, _ = _live(qs, ps, level, ntt)
+    ext = modup_ntt(d2_ntt, qs, ps, dnum, len(ql), ntt)
+    acc0, acc1 = _gathered_inner(ext, slice(None), evk_b, evk_a, rows, _mods_col(ql + ps))
+    return moddown_ntt(acc0, ql, ps, ntt), moddown_ntt(acc1, ql, ps, ntt)
 
 
 # --------------------------------------------------------------------------------------
@@ -570,48 +614,38 @@ def gen_rot_key(s, k: int, qs, ps, dnum, rng):
     return gen_switch_key(s, rns_ntt_fwd(sk, allm), qs, ps, dnum, rng)
 
 
-def rotate(ct_ntt, k: int, rot_b, rot_a, qs, ps, dnum, log_n: int):
-    """ct = (c0, c1) in NTT form over Q: (sigma_k c0 + KS0(sigma_k c1), KS1(sigma_k c1)).
+def rotate(ct_ntt, k: int, rot_b, rot_a, qs, ps, dnum, log_n: int, *, level=None, ntt=None):
+    """ct = (c0, c1) (2, level, N) in NTT form: (sigma_k c0 + KS0(sigma_k c1), KS1(sigma_k c1)).
     Decrypts to sigma_k(m) under s."""
     c0 = automorphism_ntt(ct_ntt[0], k, log_n)
     c1 = automorphism_ntt(ct_ntt[1], k, log_n)
-    ks0, ks1 = keyswitch(c1, rot_b, rot_a, qs, ps, dnum)
-    col = _mods_col(qs)
+    ks0, ks1 = keyswitch(c1, rot_b, rot_a, qs, ps, dnum, level=level, ntt=ntt)
+    col = _mods_col(_live(qs, ps, level, ntt)[0])
     return np.stack([(c0 + ks0) % col, ks1 % col])
 
 
-def rotate_hoisted(ct_ntt, ks, keys, qs, ps, dnum, log_n: int):
+def rotate_hoisted(ct_ntt, ks, keys, qs, ps, dnum, log_n: int, *, level=None, ntt=None):
     """Hoisted rotations (Halevi-Shoup), restated for gpu-fhe_amd/csrc/galois.hip
     launch_rotate_hoisted: ModUp(c1) once -- INTT, digit base conversion, NTT of every extended
     digit -- then per Galois element k with key (rot_b, rot_a): the digits gathered through
     sigma_k in the NTT domain, the inner product with the key, ModDown, plus sigma_k(c0).
     Not bit-identical to rotate() (ModUp(sigma c1) differs from sigma ModUp(c1) by multiples of
-    the digit moduli), but decrypts to sigma_k(m) the same way.  Returns [len(ks), 2, L, N]."""
-    qs = [int(q) for q in qs]
-    ps = [int(p) for p in ps]
-    allm = qs + ps
-    c1 = np.asarray(ct_ntt[1]).astype(object)
-    ext = [rns_ntt_fwd(e, allm) for e in modup(rns_ntt_inv(c1, qs), qs, ps, dnum)]
-    # the digit's own rows are c1 itself (NTT(INTT(c1)) = c1)
-    for (lo, hi), e in zip(digit_ranges(len(qs), dnum), ext):
-        e[lo:hi] = c1[lo:hi]
-    mods = _mods_col(allm)
-    col = _mods_col(qs)
+    the digit moduli), but decrypts to sigma_k(m) the same way.  ct (2, level, N) ->
+    [len(ks), 2, level, N]."""
+    ql, ps, rows, _, _ = _live(qs, ps, level, ntt)
+    ct = np.asarray(ct_ntt).astype(object)
+    ext = modup_ntt(ct[1], qs, ps, dnum, len(ql), ntt)
+    mods, col = _mods_col(ql + ps), _mods_col(ql)
     out = []
     for k, (rot_b, rot_a) in zip(ks, keys):
-        idx = automorphism_ntt_index(k, log_n)
-        acc0 = np.zeros((len(allm), c1.shape[-1]), dtype=object)
-        acc1 = np.zeros_like(acc0)
-        for j, e in enumerate(ext):
-            g = e[..., idx]
-            acc0 = (acc0 + g * np.asarray(rot_b[j]).astype(object)) % mods
-            acc1 = (acc1 + g * np.asarray(rot_a[j]).astype(object)) % mods
-        c0 = automorphism_ntt(ct_ntt[0], k, log_n)
-        out.append(np.stack([(c0 + moddown_ntt(acc0, qs, ps)) % col, moddown_ntt(acc1, qs, ps)]))
+        idx = automorphism_ntt_index(int(k), log_n)
+        acc0, acc1 = _gathered_inner(ext, idx, rot_b, rot_a, rows, mods)
+        out.append(np.stack([(ct[0][..., idx] + moddown_ntt(acc0, ql, ps, ntt)) % col,
+                             moddown_ntt(acc1, ql, ps, ntt)]))
     return np.stack(out)
 
 
-def rotate_sum_hoisted(ct_ntt, ks, keys, pts, qs, ps, dnum, log_n: int):
+def rotate_sum_hoisted(ct_ntt, ks, keys, pts, qs, ps, dnum, log_n: int, *, level=None, ntt=None):
     """sum_r pt_r * rot_{k_r}(ct) with one ModUp and one ModDown (double hoisting, the inner
     loop of a baby-step / giant-step linear transform), restated for gpu-fhe_amd/csrc/galois.hip
     launch_rotate_sum_hoisted.  pts[r]: (L + K, N) NTT form over Q u P.  Per rotation the
@@ -622,64 +656,48 @@ def rotate_sum_hoisted(ct_ntt, ks, keys, pts, qs, ps, dnum, log_n: int):
     k_r = 1 is the unrotated term (no key; keys[r] may be None): pt_r c0 joins the c0 sum and
     pt_r (P mod q_i) c1 joins A1's Q rows, so that ModDown returns pt_r c1 exactly
     (ModDown(P x + y) = x + ModDown(y)).  Decrypts to sum_r pt_r sigma_r(m) up to one ModDown's
-    rounding, not to the sum of separate rotate_hoisted outputs bit for bit.  (L, N) x 2 out."""
-    qs = [int(q) for q in qs]
-    ps = [int(p) for p in ps]
-    allm = qs + ps
-    L = len(qs)
+    rounding, not to the sum of separate rotate_hoisted outputs bit for bit.
+    ct (2, level, N) -> (2, level, N)."""
+    ql, ps, rows, _, _ = _live(qs, ps, level, ntt)
+    l = len(ql)
     P = math.prod(ps)
     c0 = np.asarray(ct_ntt[0]).astype(object)
     c1 = np.asarray(ct_ntt[1]).astype(object)
     n = c1.shape[-1]
-    mods = _mods_col(allm)
-    col = _mods_col(qs)
-    ext = None
-    if any(int(k) != 1 for k in ks):
-        ext = [rns_ntt_fwd(e, allm) for e in modup(rns_ntt_inv(c1, qs), qs, ps, dnum)]
-        for (lo, hi), e in zip(digit_ranges(L, dnum), ext):
-            e[lo:hi] = c1[lo:hi]
-    a0 = np.zeros((len(allm), n), dtype=object)
+    mods, col = _mods_col(ql + ps), _mods_col(ql)
+    ext = modup_ntt(c1, qs, ps, dnum, l, ntt) if any(int(k) != 1 for k in ks) else None
+    a0 = np.zeros((l + len(ps), n), dtype=object)
     a1 = np.zeros_like(a0)
-    s0 = np.zeros((L, n), dtype=object)
-    pcol = np.array([P % q for q in qs], dtype=object).reshape(-1, 1)
+    s0 = np.zeros((l, n), dtype=object)
+    pcol = np.array([P % q for q in ql], dtype=object).reshape(-1, 1)
     for k, key, pt in zip(ks, keys, pts):
         k = int(k)
-        pt = np.asarray(pt).astype(object)
+        pt = np.asarray(pt)[rows].astype(object)
         if k == 1:
-            s0 = (s0 + pt[:L] * c0) % col
-            a1[:L] = (a1[:L] + pt[:L] * (pcol * c1 % col)) % col
+            s0 = (s0 + pt[:l] * c0) % col
+            a1[:l] = (a1[:l] + pt[:l] * (pcol * c1 % col)) % col
             continue
-        rot_b, rot_a = key
         idx = automorphism_ntt_index(k, log_n)
-        acc0 = np.zeros((len(allm), n), dtype=object)
-        acc1 = np.zeros_like(acc0)
-        for j, e in enumerate(ext):
-            g = e[..., idx]
-            acc0 = (acc0 + g * np.asarray(rot_b[j]).astype(object)) % mods
-            acc1 = (acc1 + g * np.asarray(rot_a[j]).astype(object)) % mods
+        acc0, acc1 = _gathered_inner(ext, idx, key[0], key[1], rows, mods)
         a0 = (a0 + pt * acc0) % mods
         a1 = (a1 + pt * acc1) % mods
-        s0 = (s0 + pt[:L] * c0[..., idx]) % col
-    return np.stack([(s0 + moddown_ntt(a0, qs, ps)) % col, moddown_ntt(a1, qs, ps)])
+        s0 = (s0 + pt[:l] * c0[..., idx]) % col
+    return np.stack([(s0 + moddown_ntt(a0, ql, ps, ntt)) % col, moddown_ntt(a1, ql, ps, ntt)])
 
 
-def rotate_sum_multi(cts, ks, keys, qs, ps, dnum, log_n: int):
+def rotate_sum_multi(cts, ks, keys, qs, ps, dnum, log_n: int, *, level=None, ntt=None):
     """sum_r rot_{k_r}(cts[r]) over different ciphertexts with ONE ModDown (the giant-step sum of a
     baby-step / giant-step linear transform), restated for gpu-fhe_amd/csrc/galois.hip
     launch_rotate_sum_multi.  Per rotated term: ModUp of its own c1, the gathered inner product
     with its key added into the Q u P sums A_h, sigma_k(c0) into the c0 sum; an unrotated term
     (k = 1, no key) adds c0 and c1 themselves (exactly: ModDown(P x + y) = x + ModDown(y)).
-      out = (C0 + ModDown(A0), C1 + ModDown(A1)).  (L, N) x 2 out."""
-    qs = [int(q) for q in qs]
-    ps = [int(p) for p in ps]
-    allm = qs + ps
-    L = len(qs)
-    mods = _mods_col(allm)
-    col = _mods_col(qs)
+      out = (C0 + ModDown(A0), C1 + ModDown(A1)).  cts[r] (2, level, N) -> (2, level, N)."""
+    ql, ps, rows, _, _ = _live(qs, ps, level, ntt)
+    mods, col = _mods_col(ql + ps), _mods_col(ql)
     n = np.asarray(cts[0]).shape[-1]
-    a0 = np.zeros((len(allm), n), dtype=object)
+    a0 = np.zeros((len(ql) + len(ps), n), dtype=object)
     a1 = np.zeros_like(a0)
-    s0 = np.zeros((L, n), dtype=object)
+    s0 = np.zeros((len(ql), n), dtype=object)
     s1 = np.zeros_like(s0)
     for ct, k, key in zip(cts, ks, keys):
         k = int(k)
@@ -689,27 +707,26 @@ def rotate_sum_multi(cts, ks, keys, qs, ps, dnum, log_n: int):
             s0 = (s0 + c0) % col
             s1 = (s1 + c1) % col
             continue
-        ext = [rns_ntt_fwd(e, allm) for e in modup(rns_ntt_inv(c1, qs), qs, ps, dnum)]
-        for (lo, hi), e in zip(digit_ranges(L, dnum), ext):
-            e[lo:hi] = c1[lo:hi]
-        rot_b, rot_a = key
         idx = automorphism_ntt_index(k, log_n)
-        for j, e in enumerate(ext):
-            g = e[..., idx]
-            a0 = (a0 + g * np.asarray(rot_b[j]).astype(object)) % mods
-            a1 = (a1 + g * np.asarray(rot_a[j]).astype(object)) % mods
+        acc0, acc1 = _gathered_inner(modup_ntt(c1, qs, ps, dnum, len(ql), ntt), idx, key[0], key[1],
+                                     rows, mods)
+        a0 = (a0 + acc0) % mods
+        a1 = (a1 + acc1) % mods
         s0 = (s0 + c0[..., idx]) % col
-    return np.stack([(s0 + moddown_ntt(a0, qs, ps)) % col, (s1 + moddown_ntt(a1, qs, ps)) % col])
+    return np.stack([(s0 + moddown_ntt(a0, ql, ps, ntt)) % col,
+                     (s1 + moddown_ntt(a1, ql, ps, ntt)) % col])
 
 
-def linear_transform(ct_ntt, baby, baby_keys, giant, giant_keys, pts, qs, ps, dnum, log_n: int):
+def linear_transform(ct_ntt, baby, baby_keys, giant, giant_keys, pts, qs, ps, dnum, log_n: int, *,
+                     level=None, ntt=None):
     """Baby-step / giant-step plaintext-matrix product with both hoistings, restated for
     gpu-fhe_amd/csrc/galois.hip launch_linear_transform:
       out = sum_g rot_{giant[g]}( sum_b pts[g][b] rot_{baby[b]}(ct) ),
     each giant step's inner sum exactly rotate_sum_hoisted (one ModUp of ct shared by all of them on
     the device, one ModDown each), the outer sum exactly rotate_sum_multi (one ModDown)."""
-    inner = [rotate_sum_hoisted(ct_ntt, baby, baby_keys, row, qs, ps, dnum, log_n) for row in pts]
-    return rotate_sum_multi(inner, giant, giant_keys, qs, ps, dnum, log_n)
+    inner = [rotate_sum_hoisted(ct_ntt, baby, baby_keys, row, qs, ps, dnum, log_n, level=level,
+                                ntt=ntt) for row in pts]
+    return rotate_sum_multi(inner, giant, giant_keys, qs, ps, dnum, log_n, level=level, ntt=ntt)
 
 
 def rescale_coeff(x, moduli):
@@ -743,10 +760,10 @@ def rescale_exact(x, moduli):
     return np.stack([Y % q for q in moduli[:-1]])
 
 
-def rescale_ntt(x, moduli):
+def rescale_ntt(x, moduli, ntt=None):
     """Rescale of an NTT-form (l, N) input: INTT, divide-and-round, NTT over the l - 1 limbs."""
-    c = rns_ntt_inv(x, moduli)
-    return rns_ntt_fwd(rescale_coeff(c, moduli), moduli[:-1])
+    fwd, inv = ntt or (rns_ntt_fwd, rns_ntt_inv)
+    return fwd(rescale_coeff(inv(x, moduli), moduli), moduli[:-1])
 
 
 # ---- SURVEY.md §8(f) row 4: the fused multiply -> relinearise -> rescale pipeline ----------------
@@ -759,14 +776,16 @@ def tensor_ntt(a, b, moduli):
     return np.stack([a[0] * b[0] % qs, (a[0] * b[1] + a[1] * b[0]) % qs, a[1] * b[1] % qs])
 
 
-def mul_relin(a, b, evk_b, evk_a, qs, ps, dnum, rescale: bool):
-    """Relin(a x b) = (d0 + KS0(d2), d1 + KS1(d2)), NTT form; then optionally rescale_ntt."""
-    d = tensor_ntt(a, b, qs)
-    ks0, ks1 = keyswitch(d[2], evk_b, evk_a, qs, ps, dnum)
-    col = _mods_col(qs)
+def mul_relin(a, b, evk_b, evk_a, qs, ps, dnum, rescale: bool, *, level=None, ntt=None):
+    """a, b (2, level, N) NTT form -> Relin(a x b) = (d0 + KS0(d2), d1 + KS1(d2)), NTT form; then
+    optionally rescale_ntt to (2, level - 1, N)."""
+    ql = _live(qs, ps, level, ntt)[0]
+    d = tensor_ntt(a, b, ql)
+    ks0, ks1 = keyswitch(d[2], evk_b, evk_a, qs, ps, dnum, level=level, ntt=ntt)
+    col = _mods_col(ql)
     out = np.stack([(d[0] + ks0) % col, (d[1] + ks1) % col])
     if rescale:
-        out = np.stack([rescale_ntt(out[0], qs), rescale_ntt(out[1], qs)])
+        out = np.stack([rescale_ntt(out[0], ql, ntt), rescale_ntt(out[1], ql, ntt)])
     return out
 
 

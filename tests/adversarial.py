@@ -105,16 +105,6 @@ def conv_fraction(src, dst):
             for t in dst]
 
 
-def live_digits(L, dnum, level=None):
-    """Digit ranges over the live Q-limbs: pyoracle.digit_ranges at the top level; below it the
-    top-level width alpha = ceil(L / dnum), the last live digit cut at `level` (tests/level_ref.py
-    level_digits)."""
-    if level is None or level == L:
-        return pyoracle.digit_ranges(L, dnum)
-    alpha = -(-L // dnum)
-    return [(lo, min(level, lo + alpha)) for lo in range(0, level, alpha)]
-
-
 # ---- key-switch ---------------------------------------------------------------------------------
 
 D2_KINDS = ("zero", "qm1", "modup_worst", "alt")
@@ -123,7 +113,8 @@ D2_KINDS = ("zero", "qm1", "modup_worst", "alt")
 def ks_d2(kind, qs, ps, dnum, log_n, level=None):
     """[level][N] NTT form over the live Q-limbs qs[:level] (level None: all of qs).
     zero; qm1: q - 1 in every NTT-form word (the largest own-digit operand of the inner product);
-    modup_worst: the forward NTT of conv_worst, digit by digit (live_digits); alt: the forward NTT
+    modup_worst: the forward NTT of conv_worst, digit by digit (pyoracle.digit_ranges at the
+    level); alt: the forward NTT
     of coefficients alternating 0 and q - 1.  ps is unused (the signature of the call it feeds)."""
     qs = [int(q) for q in qs]
     L = len(qs)
@@ -134,7 +125,8 @@ def ks_d2(kind, qs, ps, dnum, log_n, level=None):
     if kind == "qm1":
         return _const_rows([q - 1 for q in ql], n)
     if kind == "modup_worst":
-        c = np.concatenate([conv_worst(ql[lo:hi], log_n) for lo, hi in live_digits(L, dnum, level)])
+        c = np.concatenate([conv_worst(ql[lo:hi], log_n)
+                            for lo, hi in pyoracle.digit_ranges(L, dnum, level)])
         return _ntt(c, ql)
     if kind == "alt":
         c = _const_rows([q - 1 for q in ql], n)

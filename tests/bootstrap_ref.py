@@ -1,5 +1,5 @@
 """References for fhecore.bootstrap: the float64 plaintext model of the pipeline, the CPU backend of
-the Bootstrapper (plain_ref.CpuBackend plus level_hoist_ref, level_ref, modraise_ref, conj_ref and
+the Bootstrapper (plain_ref.CpuBackend plus pyoracle at a level, modraise_ref, conj_ref and
 encode_ref), and the case the CPU and GPU tests share, computed once per process:
 
   log_n = 10, L = 18, 5 special primes, dnum = 4; q_0 the largest 55-bit prime of the ring, the
@@ -28,11 +28,10 @@ import numpy as np
 
 import conj_ref
 import encode_ref
-import level_hoist_ref
-import level_ref
 import modraise_ref
 import plain_ref
 import pyoracle
+import refs
 import sparse_ref
 
 LOG_N, L, NSPECIAL, DNUM = 10, 18, 5, 4
@@ -147,21 +146,19 @@ class CpuBackend(plain_ref.CpuBackend):
 
     def linear_transform(self, a, factor):
         baby, bkeys, giant, gkeys, pts = factor
-        return self._batched(lambda x: level_hoist_ref.linear_transform(
-            x, baby, bkeys, giant, gkeys, pts, self.moduli, self.ps, self.dnum, x.shape[-2],
-            self.log_n), a)
+        return self._batched(lambda x: pyoracle.linear_transform(
+            x, baby, bkeys, giant, gkeys, pts, self.moduli, self.ps, self.dnum, self.log_n,
+            level=x.shape[-2], ntt=refs.c_ntt()), a)
 
     def rescale(self, a):
-        def one(x):
-            ql = self.moduli[:x.shape[-2]]
-            return np.stack([level_ref.rescale_ntt(x[0], ql), level_ref.rescale_ntt(x[1], ql)])
-        return self._batched(one, a)
+        return self._batched(lambda x: plain_ref._rescale(x, self.moduli[:x.shape[-2]]), a)
 
     def conjugate(self, a):
         elt = (2 << self.log_n) - 1
         kb, ka = self.rot_keys[elt]
-        return self._batched(lambda x: level_ref.rotate_level(
-            x, elt, kb, ka, self.moduli, self.ps, self.dnum, x.shape[-2], self.log_n), a)
+        return self._batched(lambda x: pyoracle.rotate(
+            x, elt, kb, ka, self.moduli, self.ps, self.dnum, self.log_n, level=x.shape[-2],
+            ntt=refs.c_ntt()), a)
 
     def conj_split(self, a, c):
         return conj_ref.conj_split(a, c, self.moduli, np.asarray(a).shape[-2])

@@ -30,6 +30,8 @@ hommult_sampled_N65536_L8: BASELINE configs[2] at its full size (N = 2^16, the 8
     PCG64 and checks their sha256 first.
 ntt_N4096_L1: the O(N^2) defining sum of SURVEY.md §8a' evaluated in Python big ints (the
     reference's NTT is the identity, arithmetic.py:15-16, so it cannot pin this).
+level_refs.json (--level-refs): digests of pyoracle's key-switch family at every level; see
+    level_refs below.
 """
 import importlib
 import os
@@ -189,7 +191,31 @@ def ntt_fixture(log_n, seed):
             "seed": np.array(seed)}
 
 
+def level_refs(ops=pyoracle):
+    """level_refs.json: {"shape/op/level": sha256 of the uint64 result} of the key-switch family
+    (tests/refs.py level_cases) at every level on the worlds of tests/test_level_hoist_cpu.py and
+    tests/test_levels_cpu.py.  The committed file was written before pyoracle took level=, with
+    `ops` an adapter from these signatures onto the functions pyoracle then had at the top level
+    and the two test modules that restated them below it (both at level L, which agreed); it
+    fixes what the unified functions must compute, so regenerate it only for new cases."""
+    import json
+
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import refs
+
+    out = {}
+    for w in [refs.small_world(*shape) for shape in refs.PIN_SMALL] + [refs.hoist_world()]:
+        out.update(refs.level_digests(w, ops, refs.c_ntt()))
+    with open(os.path.join(HERE, "level_refs.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("wrote level_refs.json,", len(out), "digests")
+
+
 def main():
+    if "--level-refs" in sys.argv:  # needs no reference checkout
+        level_refs()
+        return
     arith, poly = load_reference()
     if "--sampled-only" in sys.argv:  # only the configs[2] sampled pin (the others unchanged)
         np.savez(os.path.join(HERE, "hommult_sampled_N65536_L8.npz"),

@@ -1,18 +1,19 @@
 """Reference for the level-aware plaintext arithmetic (fhe_lincomb_level, fhe_mul_plain_level;
 include/fhecore.h) in exact Python-integer arithmetic over (2, l, N) object arrays, the CPU backend
-of fhecore.polyeval built from it and tests/level_ref.py, and the Chebyshev case the CPU and GPU
+of fhecore.polyeval built from it and pyoracle.mul_relin, and the Chebyshev case the CPU and GPU
 tests share (computed once per process)."""
 import functools
 import random
 
 import numpy as np
 
-import level_ref
 import pyoracle
+import refs
 
 
 def _rescale(x, ql):
-    return np.stack([level_ref.rescale_ntt(x[0], ql), level_ref.rescale_ntt(x[1], ql)])
+    return np.stack([pyoracle.rescale_ntt(x[0], ql, refs.c_ntt()),
+                     pyoracle.rescale_ntt(x[1], ql, refs.c_ntt())])
 
 
 def lincomb_level(cts, scalars, qs, level, const=None, rescale=False):
@@ -38,7 +39,7 @@ def mul_plain_level(ct, pt, qs, level, rescale=False):
 
 
 class CpuBackend:
-    """fhecore.polyeval backend over (2, l, N) numpy arrays: level_ref.mul_relin_level and the
+    """fhecore.polyeval backend over (2, l, N) numpy arrays: pyoracle.mul_relin and the
     functions above."""
 
     def __init__(self, qs, ps, dnum, evk_b, evk_a):
@@ -46,8 +47,8 @@ class CpuBackend:
         self.evk_b, self.evk_a = evk_b, evk_a
 
     def mul_relin(self, a, b, rescale):
-        return level_ref.mul_relin_level(a, b, self.evk_b, self.evk_a, self.moduli, self.ps,
-                                         self.dnum, np.asarray(a).shape[-2], rescale)
+        return pyoracle.mul_relin(a, b, self.evk_b, self.evk_a, self.moduli, self.ps, self.dnum,
+                                  rescale, level=np.asarray(a).shape[-2], ntt=refs.c_ntt())
 
     def lincomb(self, cts, scalars, const, rescale, level):
         n = len(cts)

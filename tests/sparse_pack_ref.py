@@ -21,8 +21,8 @@ import numpy as np
 
 import bootstrap_ref as br
 import encode_ref
-import level_ref
 import pyoracle
+import refs
 
 LOG_SLOTS = 6
 PARAMS = dict(br.PARAMS, log_slots=LOG_SLOTS)
@@ -106,8 +106,9 @@ class CpuBackend(br.CpuBackend):
     def rotate(self, a, step):
         elt = pyoracle.galois_elt(step, 1 << self.log_n)
         kb, ka = self.rot_keys[elt]
-        return self._batched(lambda x: level_ref.rotate_level(
-            x, elt, kb, ka, self.moduli, self.ps, self.dnum, x.shape[-2], self.log_n), a)
+        return self._batched(lambda x: pyoracle.rotate(
+            x, elt, kb, ka, self.moduli, self.ps, self.dnum, self.log_n, level=x.shape[-2],
+            ntt=refs.c_ntt()), a)
 
     def load_factor(self, z, baby, giant, delta):
         z = np.asarray(z)

@@ -12,6 +12,7 @@ import pytest
 import adversarial as adv
 import coracle
 import pyoracle
+import refs
 
 LOG_N = 10
 N = 1 << LOG_N
@@ -169,10 +170,8 @@ def test_oracles_agree_on_the_families(bits, L, K, dnum):
 
 def test_selector_key_returns_the_digit_through_moddown():
     """select_j: acc0 = NTT(ModUp(digit j)) and acc1 = 0, so ks1 = 0 and ks0 is ModDown of the
-    extended digit; the key below the top level selects the same digit (level_ref reads its live
+    extended digit; the key below the top level selects the same digit (the level reads its live
     rows)."""
-    import level_ref
-
     L, K, dnum = 5, 2, 3
     qs, ps = _ks_chain(60, L, K)
     allm = qs + ps
@@ -187,9 +186,9 @@ def test_selector_key_returns_the_digit_through_moddown():
     # below the top: a partial last digit (level 3: digits [0, 2), [2, 3)) and level 1
     kb, ka = adv.ks_keys("select_0", allm, dnum, LOG_N)
     for level in (3, 1):
-        assert adv.live_digits(L, dnum, level) == level_ref.level_digits(level, L, dnum)
+        assert pyoracle.digit_ranges(L, dnum, level) == {3: [(0, 2), (2, 3)], 1: [(0, 1)]}[level]
         for kind in ("zero", "modup_worst"):
             d = adv.ks_d2(kind, qs, ps, dnum, LOG_N, level=level)
             assert d.shape == (level, N)
-            r0, r1 = level_ref.keyswitch_level(d, kb, ka, qs, ps, dnum, level)
+            r0, r1 = pyoracle.keyswitch(d, kb, ka, qs, ps, dnum, level=level, ntt=refs.c_ntt())
             assert not r1.any() and (kind != "zero" or not r0.any()), (level, kind)

@@ -13,9 +13,8 @@ import pytest
 
 import adversarial as adv
 import coracle
-import level_hoist_ref
-import level_ref
 import pyoracle
+import refs
 
 pytestmark = pytest.mark.gpu
 
@@ -247,7 +246,8 @@ def test_keyswitch_below_the_top_on_structured_operands(fc, spec, keys):
     dkb, dka = fc.to_device(kb), fc.to_device(ka)
     for level in (3, 1):
         d2 = np.stack([adv.ks_d2(k, qs, ps, dnum, log_n, level=level) for k in LEVEL_D2])
-        want = [level_ref.keyswitch_level(d2[i], kb, ka, qs, ps, dnum, level) for i in range(3)]
+        want = [pyoracle.keyswitch(d2[i], kb, ka, qs, ps, dnum, level=level, ntt=refs.c_ntt())
+                for i in range(3)]
         for batch in (1, 3):
             ks0, ks1 = ctx.keyswitch(fc.to_device(d2[:batch]), dkb, dka)
             g0, g1 = fc.to_host(ks0), fc.to_host(ks1)
@@ -324,7 +324,8 @@ def test_rotate_and_rotate_hoisted_on_structured_ciphertexts(fc, spec):
     # one step under the all-(t - 1) key, the conjugation under a selector
     for k in (e1, conj):
         hb, ha = w["hkeys"][k]
-        want = [level_ref.rotate_level(ct[b], k, hb, ha, qs, ps, dnum, L, log_n) for b in range(3)]
+        want = [pyoracle.rotate(ct[b], k, hb, ha, qs, ps, dnum, log_n, level=L, ntt=refs.c_ntt())
+                for b in range(3)]
         for batch in (1, 3):
             got = fc.to_host(ctx.rotate(dct[:batch], k, *w["dkeys"][k]))
             for b in range(batch):
@@ -342,9 +343,9 @@ def test_rotate_and_rotate_hoisted_on_structured_ciphertexts(fc, spec):
             assert not got[1:, b, 1].any(), (batch, CT_KINDS[b])  # the selectors' ks1
 
 
-def _sum_refs(w, level, top):
+def _sum_refs(w, level):
     """rotate_sum_hoisted, rotate_sum_multi and linear_transform references for the three
-    ciphertexts of _cts, plaintexts all t - 1: pyoracle at the top level, level_hoist_ref below."""
+    ciphertexts of _cts, plaintexts all t - 1: pyoracle at `level`."""
     ctx = w["ctx"]
     log_n, L, K, dnum, _ = w["spec"]
     qs, ps = ctx.moduli, ctx.special
@@ -353,16 +354,16 @@ def _sum_refs(w, level, top):
     others = [_cts(w, level, seed=1), _cts(w, level, seed=2)]
     pt = w["hpts"]["tm1"]
     sks, mks, baby, giant = [1, e1, e2], [e1, 1, conj], [1, e1], [e2, 1]
-    tail = (qs, ps, dnum, log_n) if top else (qs, ps, dnum, level, log_n)
-    r = pyoracle if top else level_hoist_ref
+    tail = (qs, ps, dnum, log_n)
+    at = dict(level=level, ntt=refs.c_ntt())
     out = dict(sks=sks, mks=mks, baby=baby, giant=giant, ct=ct, others=others)
-    out["sum"] = [r.rotate_sum_hoisted(ct[b], sks, _keys(w, sks, False), [pt] * 3, *tail)
-                  for b in range(3)]
-    out["multi"] = [r.rotate_sum_multi([ct[b], others[0][b], others[1][b]], mks,
-                                       _keys(w, mks, False), *tail) for b in range(3)]
-    out["lt"] = [r.linear_transform(ct[b], baby, _keys(w, baby, False), giant,
-                                    _keys(w, giant, False), [[pt, pt], [pt, pt]], *tail)
-                 for b in range(3)]
+    out["sum"] = [pyoracle.rotate_sum_hoisted(ct[b], sks, _keys(w, sks, False), [pt] * 3, *tail,
+                                              **at) for b in range(3)]
+    out["multi"] = [pyoracle.rotate_sum_multi([ct[b], others[0][b], others[1][b]], mks,
+                                              _keys(w, mks, False), *tail, **at) for b in range(3)]
+    out["lt"] = [pyoracle.linear_transform(ct[b], baby, _keys(w, baby, False), giant,
+                                           _keys(w, giant, False), [[pt, pt], [pt, pt]], *tail,
+                                           **at) for b in range(3)]
     return out
 
 
@@ -375,7 +376,7 @@ def test_rotation_sums_and_linear_transform_on_structured_ciphertexts(fc, spec, 
     ctx = w["ctx"]
     L = spec[1]
     level = L - 1 if below else L
-    r = _sum_refs(w, level, top=not below)
+    r = _sum_refs(w, level)
     dct = fc.to_device(r["ct"])
     dothers = [fc.to_device(c) for c in r["others"]]
     pt, zero = w["dpts"]["tm1"], w["dpts"]["zero"]
@@ -419,8 +420,8 @@ def test_mul_relin_on_structured_ciphertexts(fc, spec, keys):
     b = np.stack([r2, top, r2])
     da, db, dkb, dka = (fc.to_device(v) for v in (a, b, kb, ka))
     for rescale in (False, True):
-        want = [level_ref.mul_relin_level(a[i], b[i], kb, ka, qs, ps, dnum, L, rescale)
-                for i in range(3)]
+        want = [pyoracle.mul_relin(a[i], b[i], kb, ka, qs, ps, dnum, rescale, level=L,
+                                   ntt=refs.c_ntt()) for i in range(3)]
         assert not want[0].any()
         for batch in (1, 3):
             got = fc.to_host(ctx.mul_relin(da[:batch], db[:batch], dkb, dka, rescale=rescale))

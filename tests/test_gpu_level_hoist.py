@@ -1,6 +1,6 @@
 """GPU parity for the hoisted rotations, the rotation sums and the BSGS linear transform below the
 top level (fhe_rotate_hoisted_level, fhe_rotate_sum_hoisted_level, fhe_rotate_sum_multi_level,
-fhe_linear_transform_level; include/fhecore.h) against tests/level_hoist_ref.py, bit for bit: the
+fhe_linear_transform_level; include/fhecore.h) against pyoracle at the level, bit for bit: the
 levels of contexts on each path (FAST k_rot_sum with the fused ModDown, alpha = 4, dnum > 4, K > 4,
 split30, wide), batch 1 and 3 (3 is a partial group of the kernel's 2-ciphertext blocks), one key
 tensor and one plaintext tensor per context serving every level in place."""
@@ -11,10 +11,11 @@ import numpy as np
 import pytest
 
 import coracle
-import level_hoist_ref as ref
 import pyoracle
+import refs
 
 pytestmark = pytest.mark.gpu
+NTT = refs.c_ntt()
 
 
 @pytest.fixture(scope="module")
@@ -96,11 +97,11 @@ def test_rotate_sum_and_rotate_hoisted_match_the_reference(fc, i, level):
     dct = fc.to_device(ct)
     ks = [1, e1, e2, conj]
     pts = [w["dp"][r] for r in range(4)]
-    want = [ref.rotate_sum_hoisted(ct[b], ks, keys_for(w, ks, False), w["hp"], qs, ps, dnum,
-                                   level, log_n) for b in range(3)]
+    want = [pyoracle.rotate_sum_hoisted(ct[b], ks, keys_for(w, ks, False), w["hp"], qs, ps, dnum,
+                                        log_n, level=level, ntt=NTT) for b in range(3)]
     hks = [e1, conj]
-    hwant = [ref.rotate_hoisted(ct[b], hks, keys_for(w, hks, False), qs, ps, dnum, level, log_n)
-             for b in range(3)]
+    hwant = [pyoracle.rotate_hoisted(ct[b], hks, keys_for(w, hks, False), qs, ps, dnum, log_n,
+                                     level=level, ntt=NTT) for b in range(3)]
     for batch in (1, 3):
         got = fc.to_host(ctx.rotate_sum_hoisted(dct[:batch], ks, keys_for(w, ks, True), pts))
         assert got.shape == (batch, 2, level, w["n"])
@@ -121,14 +122,14 @@ def test_rotate_sum_multi_and_linear_transform_match_the_reference(fc, i, level)
            for r in range(3)]
     dcts = [fc.to_device(c) for c in cts]
     mks = [e1, 1, conj]  # three ciphertexts, one of them unrotated
-    mwant = [ref.rotate_sum_multi([c[b] for c in cts], mks, keys_for(w, mks, False), qs, ps, dnum,
-                                  level, log_n) for b in range(3)]
+    mwant = [pyoracle.rotate_sum_multi([c[b] for c in cts], mks, keys_for(w, mks, False), qs, ps,
+                                       dnum, log_n, level=level, ntt=NTT) for b in range(3)]
     baby, giant = [1, e1], [e2, 1]  # n1 = n2 = 2, an element 1 in each list
     hpts = [[w["hp"][0], w["hp"][1]], [w["hp"][2], w["hp"][3]]]
     dpts = [[w["dp"][0], w["dp"][1]], [w["dp"][2], w["dp"][3]]]
-    lwant = [ref.linear_transform(cts[0][b], baby, keys_for(w, baby, False), giant,
-                                  keys_for(w, giant, False), hpts, qs, ps, dnum, level, log_n)
-             for b in range(3)]
+    lwant = [pyoracle.linear_transform(cts[0][b], baby, keys_for(w, baby, False), giant,
+                                       keys_for(w, giant, False), hpts, qs, ps, dnum, log_n,
+                                       level=level, ntt=NTT) for b in range(3)]
     for batch in (1, 3):
         got = fc.to_host(ctx.rotate_sum_multi([c[:batch] for c in dcts], mks,
                                               keys_for(w, mks, True)))
@@ -266,8 +267,9 @@ def test_the_top_level_workspace_size_suffices_and_nothing_is_written_past_it(fc
     ct = rand(w["qs"][:level], w["log_n"], (batch, 2), seed=7100 + level)
     ks = [1, e1, e2, conj]
     got = fc.to_host(four_calls(fc, w, level, batch, seed=7100 + level)["rotate_sum_hoisted"](level))
-    assert same(got[0], ref.rotate_sum_hoisted(ct[0], ks, keys_for(w, ks, False), w["hp"], w["qs"],
-                                               w["ps"], w["dnum"], level, w["log_n"]))
+    assert same(got[0], pyoracle.rotate_sum_hoisted(ct[0], ks, keys_for(w, ks, False), w["hp"],
+                                                    w["qs"], w["ps"], w["dnum"], w["log_n"],
+                                                    level=level, ntt=NTT))
 
 
 def test_graph_replay_of_a_linear_transform_at_level_3(fc):
@@ -414,8 +416,8 @@ def test_end_to_end_linear_transform_at_level_2_under_device_keys(fc):
     assert x.shape == (2, 2, n)
     got = fc.to_host(ctx.linear_transform(x, baby, bk, giant, gk, dpts))
     hx = fc.to_host(x)
-    want = ref.linear_transform(hx, baby, [hk(k) for k in bk], giant, [hk(k) for k in gk], hpts2,
-                                qs, ps, dnum, 2, log_n)
+    want = pyoracle.linear_transform(hx, baby, [hk(k) for k in bk], giant, [hk(k) for k in gk],
+                                     hpts2, qs, ps, dnum, log_n, level=2, ntt=NTT)
     assert same(got, want)
     err = added_error(hx, got, 2)
     print(f"linear_transform added error: top level {top}, level 2 {err}")
@@ -427,14 +429,12 @@ def test_full_size_level_13_partial_digit(fc):
     512 x 128 split): rotate_sum_hoisted with 3 terms, batch 3.  Ciphertext 0 against the
     reference, the other two each against their own single-ciphertext call.  At this size the
     reference is evaluated by its C restatement: level 13's digits are digit_ranges(13, 4), so
-    level_hoist_ref.rotate_sum_hoisted is the oracle's rotate_sum_hoisted on the key and plaintext
+    rotate_sum_hoisted at that level is the top-level rotate_sum_hoisted on the key and plaintext
     rows the level reads (tests/test_level_hoist_cpu.py checks that identity word for word)."""
-    import level_ref
-
     log_n, L, K, dnum, level, B = 16, 16, 4, 4, 13, 3
     ctx = fc.Context(log_n, L=L, K=K, dnum=dnum)
     qs, ps, allm = ctx.moduli, ctx.all_moduli[L:], ctx.all_moduli
-    assert level_ref.level_digits(level, L, dnum) == pyoracle.digit_ranges(level, dnum)
+    assert pyoracle.digit_ranges(L, dnum, level) == pyoracle.digit_ranges(level, dnum)
     ct = rand(qs[:level], log_n, (B, 2), seed=61)
     ks = [ctx.galois_elt(1), 1, ctx.galois_elt(-4)]
     kb = rand(allm, log_n, (len(ks), dnum), seed=62)
@@ -449,7 +449,7 @@ def test_full_size_level_13_partial_digit(fc):
     for b in (1, 2):
         one = fc.to_host(ctx.rotate_sum_hoisted(dct[b:b + 1], ks, dkeys, dpts))
         assert (one[0] == got[b]).all(), b
-    rows = level_ref.key_rows(level, L, K)
+    rows = pyoracle.key_rows(level, L, K)
     cut = lambda v: np.ascontiguousarray(v[..., rows, :])  # noqa: E731
     want = coracle.rotate_sum_hoisted(ct[0], ks, cut(kb), cut(ka), cut(pts), qs[:level], ps, dnum)
     assert (got[0] == want).all()

@@ -1,5 +1,5 @@
 """GPU parity for the level-aware key-switch, multiply-relinearise and rotation (fhe_keyswitch_level,
-fhe_mul_relin_level, fhe_rotate_level; include/fhecore.h) against tests/level_ref.py, bit for bit:
+fhe_mul_relin_level, fhe_rotate_level; include/fhecore.h) against pyoracle at the level, bit for bit,
 every level l = 1 .. L of contexts on each key-switch path (fused lz16, split30, unfused dnum > 4,
 wide, K > 4, both sides of the fused-ModDown predicate), the top-level key read in place."""
 import ctypes
@@ -9,10 +9,11 @@ import numpy as np
 import pytest
 
 import coracle
-import level_ref
 import pyoracle
+import refs
 
 pytestmark = pytest.mark.gpu
+NTT = refs.c_ntt()
 
 
 @pytest.fixture(scope="module")
@@ -65,21 +66,20 @@ def pass_batch(fc, ctx, batch):
     return fc.load().fhe_keyswitch_pass_batch(ctx.handle, batch)
 
 
-def _keyswitch_level_c(fc, ctx, d2, kb, ka, level):
-    """fhe_keyswitch_level itself (Context.keyswitch takes today's path at level == L)."""
+def _top_level_c(fc, ctx, name, outs, *args):
+    """The C symbol `name` without a level argument, called directly on the default stream with
+    the library's own workspace (the Context methods call the *_level entry points at every level,
+    L included)."""
     import torch
     from fhecore.context import _ptr
 
     lib = fc.load()
-    batch = d2.numel() // (level * ctx.n)
-    ks0, ks1 = torch.empty_like(d2), torch.empty_like(d2)
-    ws = ctx.workspace(lib.fhe_keyswitch_workspace(ctx.handle, ctx.L,
-                                                   lib.fhe_keyswitch_pass_batch(ctx.handle, batch)))
-    rc = lib.fhe_keyswitch_level(ctx.handle, _ptr(ks0), _ptr(ks1), _ptr(d2), _ptr(kb), _ptr(ka),
-                                 level, batch, _ptr(ws), None)
+    rc = getattr(lib, name)(ctx.handle, *[_ptr(o) for o in outs],
+                            *[_ptr(a) if isinstance(a, torch.Tensor) else a for a in args],
+                            None, None)
     torch.cuda.synchronize()
     assert rc == 0, lib.fhe_last_error()
-    return ks0, ks1
+    return outs
 
 
 # (log_n, L, K, dnum, bits): alpha = 2 on the fused lz16 path, partial and full last digits;
@@ -102,7 +102,8 @@ def test_keyswitch_every_level(fc, log_n, L, K, dnum, bits):
                for b in (1, 3)}
     for level in range(1, L + 1):
         d2 = rand(qs[:level], log_n, (3,), seed=40 + level)
-        want = [level_ref.keyswitch_level(d2[i], kb, ka, qs, ps, dnum, level) for i in range(3)]
+        want = [pyoracle.keyswitch(d2[i], kb, ka, qs, ps, dnum, level=level, ntt=NTT)
+                for i in range(3)]
         for batch in (1, 3):
             # the wrapper's own workspace, then exactly fhe_keyswitch_workspace bytes and a guard
             for ws in (None, guarded[batch]):
@@ -116,8 +117,9 @@ def test_keyswitch_every_level(fc, log_n, L, K, dnum, bits):
                 assert ws is None or ws.intact(), (level, batch)
     # level == L through the level entry point: fhe_keyswitch word for word
     d2 = d(rand(qs, log_n, (3,), seed=50))
-    t0, t1 = ctx.keyswitch(d2, dkb, dka)
-    l0, l1 = _keyswitch_level_c(fc, ctx, d2, dkb, dka, L)
+    l0, l1 = ctx.keyswitch(d2, dkb, dka)
+    t0, t1 = _top_level_c(fc, ctx, "fhe_keyswitch", [ctx.empty(*d2.shape), ctx.empty(*d2.shape)],
+                          d2, dkb, dka, 3)
     assert (fc.to_host(l0) == fc.to_host(t0)).all() and (fc.to_host(l1) == fc.to_host(t1)).all()
 
 
@@ -145,7 +147,8 @@ def test_mul_relin_every_level(fc, log_n, L, K, dnum):
                                              workspace=ws.buf))
             assert got.shape == (batch, 2, level - (1 if rescale else 0), 1 << log_n)
             for i in range(batch):
-                want = level_ref.mul_relin_level(a[i], b[i], kb, ka, qs, ps, dnum, level, rescale)
+                want = pyoracle.mul_relin(a[i], b[i], kb, ka, qs, ps, dnum, rescale, level=level,
+                                          ntt=NTT)
                 assert (got[i].astype(object) == want).all(), (level, rescale, i)
                 assert (again[i].astype(object) == want).all(), (level, rescale, i, "explicit ws")
             assert ws.intact(), (level, rescale)
@@ -165,7 +168,7 @@ def test_rotate_every_level(fc, log_n, L, K, dnum):
         for level in range(1, L + 1):
             ct = rand(qs[:level], log_n, (2,), seed=80 + level)
             got = fc.to_host(ctx.rotate(d(ct), g, rb, ra))
-            want = level_ref.rotate_level(ct, g, hb, ha, qs, ps, dnum, level, log_n)
+            want = pyoracle.rotate(ct, g, hb, ha, qs, ps, dnum, log_n, level=level, ntt=NTT)
             assert (got.astype(object) == want).all(), (g, level)
             # again in exactly fhe_rotate_workspace bytes followed by a guard
             again = fc.to_host(ctx.rotate(d(ct), g, rb, ra, workspace=ws.buf))
@@ -173,9 +176,35 @@ def test_rotate_every_level(fc, log_n, L, K, dnum):
             assert ws.intact(), (g, level)
 
 
+@pytest.mark.parametrize("bits", [60, 62])
+def test_top_level_symbols_equal_their_level_twins_at_L(fc, bits):
+    """fhe_keyswitch, fhe_rotate and fhe_mul_relin, which the Context methods no longer call, are
+    fhe_*_level at level = L word for word (the hoisted four: tests/test_gpu_level_hoist.py).  The
+    smallest context the library builds, batch 1; the 62-bit chain takes the wide path."""
+    log_n, L, K, dnum = 10, 5, 2, 3
+    ctx = ctx_for(fc, log_n, L, K, dnum, bits)
+    d = fc.to_device
+    kb, ka = d(rand(ctx.all_moduli, log_n, (dnum,), seed=31)), d(rand(ctx.all_moduli, log_n,
+                                                                      (dnum,), seed=32))
+    a, b = d(rand(ctx.moduli, log_n, (1, 2), seed=33)), d(rand(ctx.moduli, log_n, (1, 2), seed=34))
+    d2 = a[:, 1].contiguous()
+    l0, l1 = ctx.keyswitch(d2, kb, ka)
+    t0, t1 = _top_level_c(fc, ctx, "fhe_keyswitch", [ctx.empty(*d2.shape), ctx.empty(*d2.shape)],
+                          d2, kb, ka, 1)
+    assert (fc.to_host(l0) == fc.to_host(t0)).all() and (fc.to_host(l1) == fc.to_host(t1)).all()
+    for g in (5, (2 << log_n) - 1):
+        top, = _top_level_c(fc, ctx, "fhe_rotate", [ctx.empty(*a.shape)], a, g, kb, ka, 1)
+        assert (fc.to_host(ctx.rotate(a, g, kb, ka)) == fc.to_host(top)).all(), g
+    for rescale in (0, 1):
+        top, = _top_level_c(fc, ctx, "fhe_mul_relin", [ctx.empty(1, 2, L - rescale, 1 << log_n)],
+                            a, b, kb, ka, 1, rescale)
+        assert (fc.to_host(ctx.mul_relin(a, b, kb, ka, rescale=bool(rescale))) ==
+                fc.to_host(top)).all(), rescale
+
+
 def test_depth_chain_under_real_keys(fc):
     """x <- mul_relin(x, enc(m_i) cut to x's level, rescale) three times, level 4 -> 1, with keys
-    from ctx.keygen_*: every intermediate equals the level_ref chain bit for bit and the result
+    from ctx.keygen_*: every intermediate equals the pyoracle chain bit for bit and the result
     decrypts to the product of the monomials at the tracked scale.  Delta = 2^50 with 60-bit primes
     leaves scale ~2^20 at level 1 (|m| <= 81, far below q_0 / 2); the bound is the 1e-3 of the
     tracked scale that tests/test_gpu_pipeline.py uses for one level."""
@@ -210,8 +239,8 @@ def test_depth_chain_under_real_keys(fc):
     # the oracle chain alone, on the CPU
     ref, chain, scale = hcts[0], [], float(delta)
     for i, level in enumerate((4, 3, 2)):
-        ref = level_ref.mul_relin_level(ref, hcts[i + 1][:, :level], hb, ha, qs, ps, dnum, level,
-                                        True)
+        ref = pyoracle.mul_relin(ref, hcts[i + 1][:, :level], hb, ha, qs, ps, dnum, True,
+                                 level=level, ntt=NTT)
         chain.append(ref)
         scale = scale * delta / qs[level - 1]
     coef, expo = 1, 0
@@ -241,14 +270,14 @@ def test_full_size_partial_last_digit(fc):
     log_n, L, K, dnum, level, batch = 16, 16, 4, 4, 13, 2
     ctx = ctx_for(fc, log_n, L, K, dnum)
     qs, ps = ctx.moduli, ctx.all_moduli[L:]
-    assert level_ref.level_digits(level, L, dnum) == pyoracle.digit_ranges(level, dnum)
+    assert pyoracle.digit_ranges(L, dnum, level) == pyoracle.digit_ranges(level, dnum)
     kb = rand(ctx.all_moduli, log_n, (dnum,), seed=91)
     ka = rand(ctx.all_moduli, log_n, (dnum,), seed=92)
     d2 = rand(qs[:level], log_n, (batch,), seed=93)
     d = fc.to_device
     ks0, ks1 = ctx.keyswitch(d(d2), d(kb), d(ka))
     g0, g1 = fc.to_host(ks0), fc.to_host(ks1)
-    rows = level_ref.key_rows(level, L, K)
+    rows = pyoracle.key_rows(level, L, K)
     skb, ska = np.ascontiguousarray(kb[:, rows]), np.ascontiguousarray(ka[:, rows])
     for i in range(batch):
         w0, w1 = coracle.keyswitch(d2[i], skb, ska, qs[:level], ps, dnum)

@@ -1,24 +1,27 @@
-"""tests/level_hoist_ref.py, the reference of the hoisted rotations, rotation sums and the BSGS
-linear transform below the top level, checked on the CPU: at level = L it is the oracle word for
-word, and under real keys each of the four results decrypts at every level l = 1 .. L to the
-expected sum of plaintext times rotated message.
+"""pyoracle's level= argument, the reference of the key-switch family below the top level, checked
+on the CPU: every result at every level is pinned to what the functions it replaced computed, and
+under real keys each of the four hoisted results decrypts at every level l = 1 .. L to the expected
+sum of plaintext times rotated message.
 
 The decryption error bound is measured, not fixed: the error of the same inputs at l = L (the path
 already trusted) is the yardstick and every lower level must stay within 4x of it -- dropping
 digits removes noise terms, and two bits cover the different rounding of a partial last digit.
 Measured on this file's inputs (max |decryption - expectation| over the coefficients, l = L and
 the worst l < L): see DESIGN.md §3 "Hoisted forms below the top"."""
-import random
+import json
+import os
 
 import numpy as np
 import pytest
 
 import coracle
-import level_hoist_ref as ref
 import pyoracle
+import refs
+from refs import cut
 
 LOG_N, L, K, DNUM = 10, 5, 2, 3
 N = 1 << LOG_N
+NTT = refs.c_ntt()
 
 
 def sigma_int(m, k):
@@ -46,33 +49,7 @@ def add_int(a, b):
 
 @pytest.fixture(scope="module")
 def world():
-    """Moduli, a ternary secret, three real ciphertexts, rotation keys and plaintext diagonals
-    (ranges as in tests/test_gpu_rotsum.py), built once."""
-    mods = pyoracle.gen_moduli(LOG_N, L + K, 60)
-    qs, ps = [int(q) for q in mods[:L]], [int(p) for p in mods[L:]]
-    allm = qs + ps
-    rng = random.Random(2024)
-    s = [rng.randrange(-1, 2) for _ in range(N)]
-    ntt = lambda v, m: coracle.ntt_fwd(np.asarray(pyoracle._to_rns(v, m), dtype=np.uint64),  # noqa: E731
-                                       m).astype(object)
-    s_n = ntt(s, qs)
-    col = pyoracle._mods_col(qs)
-    cts, msgs = [], []
-    for _ in range(3):
-        m = [rng.randrange(-1000, 1000) for _ in range(N)]
-        a = np.stack([np.array([rng.randrange(q) for _ in range(N)], dtype=object) for q in qs])
-        e = ntt([rng.randrange(-3, 4) for _ in range(N)], qs)
-        cts.append(np.stack([(-a * s_n + e + ntt(m, qs)) % col, a]).astype(np.uint64))
-        msgs.append(m)
-    ks = [1, pyoracle.galois_elt(1, N), pyoracle.galois_elt(-2, N), 2 * N - 1]
-    keys = {}
-    for k in ks[1:]:
-        kb, ka = pyoracle.gen_rot_key(s, k, qs, ps, DNUM, rng)
-        keys[k] = (kb.astype(np.uint64), ka.astype(np.uint64))
-    pt_int = [[rng.randrange(-3, 4) for _ in range(N)] for _ in range(4)]
-    pts = [coracle.ntt_fwd(np.asarray(pyoracle._to_rns(p, allm), dtype=np.uint64), allm)
-           for p in pt_int]
-    return dict(qs=qs, ps=ps, s_n=s_n, cts=cts, msgs=msgs, ks=ks, keys=keys, pt_int=pt_int, pts=pts)
+    return refs.hoist_world(LOG_N, L, K, DNUM)
 
 
 def decrypt(ct, w, level):
@@ -86,22 +63,18 @@ def error(ct, w, level, expect):
     return max(abs(int(x) - e) for x, e in zip(decrypt(ct, w, level), expect))
 
 
-def cut(ct, level):
-    return np.ascontiguousarray(np.asarray(ct)[..., :level, :])
-
-
 # ---- the four operations at a level, each -> [(ciphertext, expected message), ...] -------------
 def op_rotate_hoisted(w, level):
     ks = w["ks"][1:3] + w["ks"][3:]
-    out = ref.rotate_hoisted(cut(w["cts"][0], level), ks, [w["keys"][k] for k in ks], w["qs"],
-                             w["ps"], DNUM, level, LOG_N)
+    out = pyoracle.rotate_hoisted(cut(w["cts"][0], level), ks, [w["keys"][k] for k in ks], w["qs"],
+                                  w["ps"], DNUM, LOG_N, level=level, ntt=NTT)
     return [(o, sigma_int(w["msgs"][0], k)) for o, k in zip(out, ks)]
 
 
 def op_rotate_sum_hoisted(w, level):
     ks = w["ks"]
-    out = ref.rotate_sum_hoisted(cut(w["cts"][0], level), ks, [w["keys"].get(k) for k in ks],
-                                 w["pts"], w["qs"], w["ps"], DNUM, level, LOG_N)
+    out = pyoracle.rotate_sum_hoisted(cut(w["cts"][0], level), ks, [w["keys"].get(k) for k in ks],
+                                      w["pts"], w["qs"], w["ps"], DNUM, LOG_N, level=level, ntt=NTT)
     expect = [0] * N
     for k, p in zip(ks, w["pt_int"]):
         expect = add_int(expect, negacyclic_int(p, sigma_int(w["msgs"][0], k)))
@@ -110,8 +83,9 @@ def op_rotate_sum_hoisted(w, level):
 
 def op_rotate_sum_multi(w, level):
     ks = [w["ks"][1], 1, w["ks"][3]]
-    out = ref.rotate_sum_multi([cut(c, level) for c in w["cts"]], ks,
-                               [w["keys"].get(k) for k in ks], w["qs"], w["ps"], DNUM, level, LOG_N)
+    out = pyoracle.rotate_sum_multi([cut(c, level) for c in w["cts"]], ks,
+                                    [w["keys"].get(k) for k in ks], w["qs"], w["ps"], DNUM, LOG_N,
+                                    level=level, ntt=NTT)
     expect = [0] * N
     for k, m in zip(ks, w["msgs"]):
         expect = add_int(expect, sigma_int(m, k))
@@ -121,9 +95,10 @@ def op_rotate_sum_multi(w, level):
 def op_linear_transform(w, level):
     baby, giant = [1, w["ks"][1]], [1, w["ks"][2]]
     pts = [w["pts"][:2], w["pts"][2:]]
-    out = ref.linear_transform(cut(w["cts"][0], level), baby, [w["keys"].get(k) for k in baby],
-                               giant, [w["keys"].get(k) for k in giant], pts, w["qs"], w["ps"],
-                               DNUM, level, LOG_N)
+    out = pyoracle.linear_transform(cut(w["cts"][0], level), baby,
+                                    [w["keys"].get(k) for k in baby], giant,
+                                    [w["keys"].get(k) for k in giant], pts, w["qs"], w["ps"], DNUM,
+                                    LOG_N, level=level, ntt=NTT)
     expect = [0] * N
     for g, kg in enumerate(giant):
         inner = [0] * N
@@ -138,25 +113,26 @@ OPS = {"rotate_hoisted": op_rotate_hoisted, "rotate_sum_hoisted": op_rotate_sum_
        "rotate_sum_multi": op_rotate_sum_multi, "linear_transform": op_linear_transform}
 
 
-def test_top_level_is_the_oracle_word_for_word(world):
-    w = world
-    qs, ps, ct = w["qs"], w["ps"], w["cts"][0]
-    ks = w["ks"]
-    rk = ks[1:]
-    assert (ref.rotate_hoisted(ct, rk, [w["keys"][k] for k in rk], qs, ps, DNUM, L, LOG_N) ==
-            pyoracle.rotate_hoisted(ct, rk, [w["keys"][k] for k in rk], qs, ps, DNUM, LOG_N)).all()
-    keys = [w["keys"].get(k) for k in ks]
-    assert (ref.rotate_sum_hoisted(ct, ks, keys, w["pts"], qs, ps, DNUM, L, LOG_N) ==
-            pyoracle.rotate_sum_hoisted(ct, ks, keys, w["pts"], qs, ps, DNUM, LOG_N)).all()
-    mk = [ks[1], 1, ks[3]]
-    mkeys = [w["keys"].get(k) for k in mk]
-    assert (ref.rotate_sum_multi(w["cts"], mk, mkeys, qs, ps, DNUM, L, LOG_N) ==
-            pyoracle.rotate_sum_multi(w["cts"], mk, mkeys, qs, ps, DNUM, LOG_N)).all()
-    baby, giant = [1, ks[1]], [1, ks[2]]
-    bk, gk = [w["keys"].get(k) for k in baby], [w["keys"].get(k) for k in giant]
-    pts = [w["pts"][:2], w["pts"][2:]]
-    assert (ref.linear_transform(ct, baby, bk, giant, gk, pts, qs, ps, DNUM, L, LOG_N) ==
-            pyoracle.linear_transform(ct, baby, bk, giant, gk, pts, qs, ps, DNUM, LOG_N)).all()
+def _pinned():
+    with open(os.path.join(os.path.dirname(__file__), "golden", "level_refs.json")) as f:
+        return json.load(f)
+
+
+def test_every_operation_at_every_level_is_what_the_parent_of_the_unification_computed(world):
+    """tests/golden/level_refs.json holds the SHA-256 of every result of the key-switch family at
+    every level on this file's world and on the two shapes of tests/test_levels_cpu.py, computed
+    before pyoracle took level= by the two sets of functions it replaced
+    (tests/golden/make_golden.py level_refs).  The unified functions must reproduce each: with the C transforms everywhere, and
+    at log_n = 6 with ntt=None as well, the pure-Python definition."""
+    want = _pinned()
+    got = refs.level_digests(world, pyoracle, NTT)
+    for shape in refs.PIN_SMALL:
+        small = refs.small_world(*shape)
+        pure = refs.level_digests(small, pyoracle, None)
+        assert refs.level_digests(small, pyoracle, NTT) == pure, shape
+        got.update(pure)
+    assert got.keys() == want.keys()
+    assert [k for k in want if got[k] != want[k]] == []
 
 
 @pytest.mark.parametrize("name", list(OPS))
@@ -176,11 +152,9 @@ def test_a_level_whose_digits_are_a_shorter_chains_is_the_c_oracle_on_the_rows_i
     reference must equal the C restatement of rotate_sum_hoisted run on that chain with the key
     and plaintext rows the level reads (how tests/test_gpu_level_hoist.py evaluates the reference
     at N = 2^16)."""
-    import level_ref
-
     w, level, dn = world, 4, 2
-    assert level_ref.level_digits(level, L, DNUM) == pyoracle.digit_ranges(level, dn)
-    rows = level_ref.key_rows(level, L, K)
+    assert pyoracle.digit_ranges(L, DNUM, level) == pyoracle.digit_ranges(level, dn)
+    rows = pyoracle.key_rows(level, L, K)
     ks = w["ks"]
     first = w["keys"][ks[1]]
     kb = np.stack([(w["keys"].get(k) or first)[0] for k in ks])[:, :dn][:, :, rows]
@@ -189,6 +163,6 @@ def test_a_level_whose_digits_are_a_shorter_chains_is_the_c_oracle_on_the_rows_i
     ct = cut(w["cts"][0], level)
     want = coracle.rotate_sum_hoisted(ct, ks, np.ascontiguousarray(kb), np.ascontiguousarray(ka),
                                       np.ascontiguousarray(pts), w["qs"][:level], w["ps"], dn)
-    got = ref.rotate_sum_hoisted(ct, ks, [w["keys"].get(k) for k in ks], w["pts"], w["qs"],
-                                 w["ps"], DNUM, level, LOG_N)
+    got = pyoracle.rotate_sum_hoisted(ct, ks, [w["keys"].get(k) for k in ks], w["pts"], w["qs"],
+                                      w["ps"], DNUM, LOG_N, level=level, ntt=NTT)
     assert (got == want.astype(object)).all()

@@ -1,24 +1,12 @@
-"""Level-aware key-switch without a GPU: the reference restatement itself (tests/level_ref.py) is
-pinned against real relinearisation keys and against the oracle's own key-switch wherever the
-truncated digit ranges coincide with those of a shorter chain, and the new C entry points
-(fhe_keyswitch_level, fhe_mul_relin_level, fhe_rotate_level) refuse a null context."""
-import random
-
+"""Level-aware key-switch without a GPU: pyoracle.keyswitch at a level is pinned against real
+relinearisation keys and against its own top-level form wherever the truncated digit ranges coincide
+with those of a shorter chain, and the C entry points (fhe_keyswitch_level, fhe_mul_relin_level,
+fhe_rotate_level) refuse a null context."""
 import numpy as np
 import pytest
 
-import level_ref
 import pyoracle
-
-
-def _setup(log_n, L, K, dnum, seed):
-    n = 1 << log_n
-    m = pyoracle.gen_moduli(log_n, L + K)
-    qs, ps = [int(q) for q in m[:L]], [int(p) for p in m[L:]]
-    rng = random.Random(seed)
-    s = [rng.randrange(-1, 2) for _ in range(n)]
-    evk_b, evk_a = pyoracle.gen_relin_key(s, qs, ps, dnum, rng)
-    return n, qs, ps, rng, s, evk_b, evk_a
+import refs
 
 
 @pytest.mark.parametrize("log_n,L,K,dnum,coincide_at_least", [(6, 5, 2, 3, {2, 3, 4, 5}),
@@ -28,13 +16,14 @@ def test_keyswitch_level_switches_the_key_at_every_level(log_n, L, K, dnum, coin
     on the centred error: the restatement measured at most 6 bits at (N, L, K, dnum) = (64, 5, 2, 3)
     (ternary s, errors in [-3, 3], the ModDown rounding), so 4 bits of margin for another seed.
     Where some dnum' makes pyoracle.digit_ranges(l, dnum') equal the truncated ranges, the result
-    equals pyoracle.keyswitch on the sliced key word for word."""
-    n, qs, ps, rng, s, evk_b, evk_a = _setup(log_n, L, K, dnum, seed=20 + L)
+    equals the top-level pyoracle.keyswitch of the l-limb chain on the sliced key word for word."""
+    n, qs, ps, rng, s, evk_b, evk_a = refs.relin_setup(log_n, L, K, dnum, seed=20 + L)
     coincided = set()
     for level in range(1, L + 1):
         ql = qs[:level]
         d2 = np.stack([np.array([rng.randrange(q) for _ in range(n)], dtype=object) for q in ql])
-        ks0, ks1 = level_ref.keyswitch_level(d2, evk_b, evk_a, qs, ps, dnum, level)
+        ks0, ks1 = pyoracle.keyswitch(d2, evk_b, evk_a, qs, ps, dnum, level=level,
+                                      ntt=refs.c_ntt())
         col = pyoracle._mods_col(ql)
         s_n = pyoracle.rns_ntt_fwd(pyoracle._to_rns(s, ql), ql)
         diff = (ks0 + ks1 * s_n - d2 * s_n * s_n) % col
@@ -42,8 +31,8 @@ def test_keyswitch_level_switches_the_key_at_every_level(log_n, L, K, dnum, coin
         bits = max(abs(int(v)) for v in err).bit_length()
         print(f"L={L} dnum={dnum} level={level} error bits {bits}")
         assert bits <= 10, (level, bits)
-        digits = level_ref.level_digits(level, L, dnum)
-        rows = level_ref.key_rows(level, L, K)
+        digits = pyoracle.digit_ranges(L, dnum, level)
+        rows = pyoracle.key_rows(level, L, K)
         for dn in range(1, level + 1):
             if pyoracle.digit_ranges(level, dn) != digits:
                 continue
@@ -56,12 +45,12 @@ def test_keyswitch_level_switches_the_key_at_every_level(log_n, L, K, dnum, coin
 
 
 def test_level_digits_and_key_rows():
-    assert level_ref.level_digits(5, 5, 3) == pyoracle.digit_ranges(5, 3)
-    assert level_ref.level_digits(3, 5, 3) == [(0, 2), (2, 3)]
-    assert level_ref.level_digits(5, 16, 4) == [(0, 4), (4, 5)]  # no dnum' gives these ranges
+    assert pyoracle.digit_ranges(5, 3, 5) == pyoracle.digit_ranges(5, 3)
+    assert pyoracle.digit_ranges(5, 3, 3) == [(0, 2), (2, 3)]
+    assert pyoracle.digit_ranges(16, 4, 5) == [(0, 4), (4, 5)]  # no dnum' gives these ranges
     assert all(pyoracle.digit_ranges(5, dn) != [(0, 4), (4, 5)] for dn in range(1, 6))
-    assert level_ref.level_digits(13, 16, 4) == pyoracle.digit_ranges(13, 4)
-    assert level_ref.key_rows(2, 5, 2) == [0, 1, 5, 6]
+    assert pyoracle.digit_ranges(16, 4, 13) == pyoracle.digit_ranges(13, 4)
+    assert pyoracle.key_rows(2, 5, 2) == [0, 1, 5, 6]
 
 
 def test_level_entry_points_refuse_a_null_context():
