@@ -614,6 +614,52 @@ int fhe_mul_relin_level(const fhe_ctx* c, uint64_t* out, const uint64_t* a, cons
   return launch_mul_relin(c, out, a, b, evk_b, evk_a, level, batch, rescale != 0, ws, hs(s));
 }
 
+int fhe_mul_sum_relin_level(const fhe_ctx* c, uint64_t* out, const uint64_t* const* a,
+                            const uint32_t* a_levels, const uint64_t* const* b,
+                            const uint32_t* b_levels, const uint64_t* evk_b, const uint64_t* evk_a,
+                            uint32_t level, uint32_t count, uint32_t batch, int rescale, void* ws,
+                            fhe_stream_t s) {
+  int rc = check_level(c, level, "fhe_mul_sum_relin_level");
+  if (rc) return rc;
+  if (c->K == 0) {
+    set_error("fhe_mul_sum_relin_level: context has no special primes (K = 0)");
+    return kInvalid;
+  }
+  if (count == 0 || count > kMulSumMax) {
+    set_error("fhe_mul_sum_relin_level: count must be 1..16");
+    return kInvalid;
+  }
+  if (rescale && level < 2) {
+    set_error("fhe_mul_sum_relin_level: rescale needs level >= 2");
+    return kInvalid;
+  }
+  if (!out || !a || !a_levels || !b || !b_levels || !evk_b || !evk_a) {
+    set_error("fhe_mul_sum_relin_level: null output, ciphertext array, level array or key");
+    return kInvalid;
+  }
+  const uint64_t out_words = (uint64_t)batch * 2 * (level - (rescale ? 1 : 0)) * c->n;
+  for (uint32_t t = 0; t < count; ++t) {
+    if (!a[t] || !b[t]) {
+      set_error("fhe_mul_sum_relin_level: null ciphertext pointer in term " + std::to_string(t));
+      return kInvalid;
+    }
+    if (a_levels[t] < level || a_levels[t] > c->L || b_levels[t] < level || b_levels[t] > c->L) {
+      set_error("fhe_mul_sum_relin_level: the levels of term " + std::to_string(t) +
+                " must be in [level, L]");
+      return kInvalid;
+    }
+    if (spans_overlap(out, out_words, a[t], (uint64_t)batch * 2 * a_levels[t] * c->n) ||
+        spans_overlap(out, out_words, b[t], (uint64_t)batch * 2 * b_levels[t] * c->n)) {
+      set_error("fhe_mul_sum_relin_level: out overlaps an input of term " + std::to_string(t));
+      return kInvalid;
+    }
+  }
+  if (batch == 0) return kOk;
+  if ((rc = ensure_ws(c, mul_relin_workspace_bytes(c, ks_pass_batch(c, batch)), &ws, hs(s)))) return rc;
+  return launch_mul_sum_relin(c, out, a, a_levels, b, b_levels, evk_b, evk_a, level, count, batch,
+                              rescale != 0, ws, hs(s));
+}
+
 size_t fhe_lincomb_workspace(const fhe_ctx* c, uint32_t batch) {
   return c ? lincomb_workspace_bytes(c, batch) : 0;
 }

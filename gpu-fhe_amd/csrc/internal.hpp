@@ -525,6 +525,13 @@ int launch_mul_relin(const fhe_ctx* c, u64* out, const u64* a, const u64* b, con
                      const u64* evk_a, u32 level, u32 batch, bool rescale, void* ws,
                      hipStream_t s);
 size_t mul_relin_workspace_bytes(const fhe_ctx* c, u32 batch);
+// out = [rescale]( relin( sum_i a[i] x b[i] ) ): a[i] [batch][2][a_levels[i]][N], b[i] likewise,
+// each cut to `level` through its own stride; mul_relin's workspace and passes
+constexpr u32 kMulSumMax = 16;
+int launch_mul_sum_relin(const fhe_ctx* c, u64* out, const u64* const* a, const u32* a_levels,
+                         const u64* const* b, const u32* b_levels, const u64* evk_b,
+                         const u64* evk_a, u32 level, u32 count, u32 batch, bool rescale,
+                         void* ws, hipStream_t s);
 
 // caller workspace, else the context's internal one grown to `bytes` (capi.cpp); an error while
 // `s` is capturing a graph

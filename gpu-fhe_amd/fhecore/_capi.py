@@ -99,6 +99,8 @@ SIGNATURES = {
                                ctypes.POINTER(_u32), ctypes.POINTER(_i32), _vp]),
     "fhe_mul_relin_workspace": (_sz, [_vp, _u32]),
     "fhe_mul_relin": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _vp, _vp]),
+    "fhe_mul_sum_relin_level": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32,
+                                       _i32, _vp, _vp]),
     "fhe_lincomb_workspace": (_sz, [_vp, _u32]),
     "fhe_lincomb_level": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _i32, _u32, _u32, _u32, _i32, _vp,
                                  _vp]),

@@ -640,6 +640,48 @@ class Context:
                                           _stream(a)), "fhe_mul_relin_level")
         return out
 
+    def mul_sum_relin(self, a_list, b_list, evk_b, evk_a, rescale: bool = True, level=None,
+                      workspace=None, out=None):
+        """[rescale]( Relin( sum_i a_list[i] x b_list[i] ) ) with one key-switch and one rescale
+        whatever the number of terms (fhe_mul_sum_relin_level; up to 16 terms).  Every operand
+        [..., 2, l, N] NTT form with one leading (batch) shape and any level l >= level (default:
+        the lowest of them), cut to `level` limbs on the fly; operands may be one tensor (squares,
+        a shared factor).  Returns [..., 2, level, N], or with rescale [..., 2, level - 1, N]; out
+        must not overlap an operand.  workspace: fhe_mul_relin_workspace(ctx, pass) bytes; None
+        takes the context's internal one, which is refused while a Graph is capturing."""
+        if not a_list or len(a_list) != len(b_list):
+            raise ValueError("mul_sum_relin: two lists of one length, at least one term")
+        la = [self._ct_level(c, "mul_sum_relin") for c in a_list]
+        lb = [self._ct_level(c, "mul_sum_relin") for c in b_list]
+        ref = a_list[0]
+        lead = tuple(ref.shape[:-3])
+        for c in (*a_list, *b_list):
+            if tuple(c.shape[:-3]) != lead or c.device != ref.device:
+                raise ValueError("mul_sum_relin: ciphertexts of one batch shape on one device")
+        if tuple(evk_b.shape) != (self.dnum, self.L + self.K, self.n) or evk_a.shape != evk_b.shape:
+            raise ValueError("mul_sum_relin: key must be [dnum, L + K, N]")
+        level = min(la + lb) if level is None else int(level)
+        count = len(a_list)
+        batch = ref.numel() // (2 * la[0] * self.n)
+        shape = (*lead, 2, level - (1 if rescale else 0), self.n)
+        if out is None:
+            out = _empty(shape, dtype=ref.dtype, device=ref.device)
+        else:
+            _check_out(out, ref, shape, "mul_sum_relin: out")
+        lib = load()
+        ws = workspace if workspace is not None else self.workspace(
+            lib.fhe_mul_relin_workspace(self._ptr, lib.fhe_keyswitch_pass_batch(self._ptr, batch)))
+        a_arr = (ctypes.c_void_p * count)(*[c.data_ptr() for c in a_list])
+        b_arr = (ctypes.c_void_p * count)(*[c.data_ptr() for c in b_list])
+        la_arr = (ctypes.c_uint32 * count)(*la)
+        lb_arr = (ctypes.c_uint32 * count)(*lb)
+        with torch.cuda.device(self.device):
+            check(lib.fhe_mul_sum_relin_level(self._ptr, _ptr(out), a_arr, la_arr, b_arr, lb_arr,
+                                              _ptr(evk_b), _ptr(evk_a), level, count, batch,
+                                              int(rescale), _ptr(ws), _stream(ref)),
+                  "fhe_mul_sum_relin_level")
+        return out
+
     # ---- plaintext arithmetic at any level (fhe_lincomb_level / fhe_mul_plain_level) --------
     def encode_scalars(self, values, delta=1.0, exact: bool = False):
         """Device table [len(values), L] of round(v * delta) mod q_j (Python integers, negative

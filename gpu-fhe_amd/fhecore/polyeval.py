@@ -33,6 +33,8 @@ A backend has
     mul_relin(a, b, rescale)                 a, b at one level -> Relin(a b) [rescaled]
     lincomb(cts, ints, const, rescale, level)  sum ints[i] cts[i] (+ ints[len(cts)]) at `level`
     drop_level(a, level)
+    mul_sum_relin(as_, bs, rescale, level)   Relin(sum as_[i] bs[i]) at `level` [rescaled]; operands
+                                             at any level >= level (inner_product only)
 on its own ciphertext arrays [..., 2, l, N].
 """
 from __future__ import annotations
@@ -69,6 +71,10 @@ class GpuBackend:
 
     def drop_level(self, a, level):
         return self.ctx.drop_level(a, level)
+
+    def mul_sum_relin(self, as_, bs, rescale, level):
+        return self.ctx.mul_sum_relin(as_, bs, self.key[0], self.key[1], rescale=rescale,
+                                      level=level)
 
 
 def _ilog2_ceil(k: int) -> int:
@@ -247,3 +253,22 @@ def eval_mod(backend, ct: Ct, K: int, degree: int = 31, double_angles: int = 2) 
         d = backend.lincomb([p.data], [2, -round(p.scale)], True, False, p.level)
         out = Ct(d, p.level, p.scale)
     return Ct(out.data, out.level, out.scale * Fraction(2.0 * math.pi))
+
+
+def inner_product(backend, xs, ys) -> Ct:
+    """sum_i xs[i] * ys[i] over two lists of Ct (up to 16 terms) with ONE relinearisation and ONE
+    rescale (backend.mul_sum_relin; fhe_mul_sum_relin_level): less work and less noise than a
+    mul_relin per term.  Every product xs[i].scale * ys[i].scale must be one scale (ValueError
+    otherwise: mismatched scales are never added silently); the sum is taken at the lowest level l
+    of the operands and returned at level l - 1 with scale s_x s_y / q_{l-1}."""
+    if not xs or len(xs) != len(ys):
+        raise ValueError("inner_product: two lists of one length, at least one term")
+    scale = Fraction(xs[0].scale) * Fraction(ys[0].scale)
+    for x, y in zip(xs, ys):
+        if Fraction(x.scale) * Fraction(y.scale) != scale:
+            raise ValueError("inner_product: the products do not share one scale")
+    lv = min(c.level for c in (*xs, *ys))
+    if lv < 2 or lv > len(backend.moduli):
+        raise ValueError(f"inner_product: the lowest level is {lv}: the rescale needs 2 .. L")
+    d = backend.mul_sum_relin([x.data for x in xs], [y.data for y in ys], True, lv)
+    return Ct(d, lv - 1, scale / int(backend.moduli[lv - 1]))

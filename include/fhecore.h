@@ -486,6 +486,35 @@ int fhe_mul_relin(const fhe_ctx* ctx, uint64_t* out, const uint64_t* a, const ui
                   const uint64_t* evk_b, const uint64_t* evk_a, uint32_t batch, int rescale,
                   void* workspace, fhe_stream_t stream);
 
+/* ---- sum of ciphertext products with one relinearisation (lazy relinearisation) ---------------
+ * Everything in NTT form, canonical residues in and out, l = level live Q-limbs:
+ *   D_k = sum_{i < count} d_k(a[i]|_l, b[i]|_l) mod q_j   (k = 0, 1, 2),
+ *   d   = (a0 b0, a0 b1 + a1 b0, a1 b1),
+ *   out = (D_0 + KS0(D_2), D_1 + KS1(D_2)),
+ * KS = fhe_keyswitch_level at `level` with the caller's top-level key read in place; with
+ * rescale != 0, out then goes through fhe_rescale(nlimbs = level, ntt_form = 1).  One key-switch
+ * and one rescale rounding whatever the count.  The canonical result does not depend on the order
+ * of the terms; count == 1 with a_levels[0] == b_levels[0] == level is bit-identical to
+ * fhe_mul_relin_level.
+ * count in 1..16.  a / b and a_levels / b_levels are host arrays of `count` entries: a[i]
+ * [batch][2][a_levels[i]][N], b[i] [batch][2][b_levels[i]][N] with level <= each <= L, every term
+ * read through its own stride (the level-drop rule of fhe_lincomb_level).  The inputs may alias
+ * each other in any way (squares a[i] == b[i], an operand shared by several terms).  out
+ * [batch][2][level][N], or [batch][2][level - 1][N] with rescale.
+ * Errors (FHE_EINVAL before any launch): K == 0; a null pointer, also inside a / b; count 0 or
+ * above 16; level 0 or above L; an input level below `level` or above L; rescale with level < 2;
+ * any overlap of out with any input; workspace == NULL while the stream is capturing.  batch == 0
+ * is a no-op.
+ * Workspace: fhe_mul_relin_workspace(ctx, fhe_keyswitch_pass_batch(ctx, batch)) bytes are
+ * sufficient at every level and count (NULL: the internal workspace).  With an explicit workspace
+ * the call is capture-safe: the pointers and strides travel in the kernel arguments, nothing is
+ * allocated, copied or synchronised.  A large batch runs in passes like fhe_mul_relin. */
+int fhe_mul_sum_relin_level(const fhe_ctx* ctx, uint64_t* out, const uint64_t* const* a,
+                            const uint32_t* a_levels, const uint64_t* const* b,
+                            const uint32_t* b_levels, const uint64_t* evk_b, const uint64_t* evk_a,
+                            uint32_t level, uint32_t count, uint32_t batch, int rescale,
+                            void* workspace, fhe_stream_t stream);
+
 /* ---- plaintext arithmetic over l <= L limbs: scalars, constants, plaintexts, level drop --------
  * The leaves of a polynomial evaluation (CKKS bootstrapping's EvalMod) in one pass each, under the
  * rule of the _level block further up: `level` = l live Q-limbs, 1 <= l <= L, NTT form, canonical

@@ -332,6 +332,41 @@ class Evaluator {
           "fhe_mul_relin_level");
     return out;
   }
+  // [rescale]( Relin( sum_i a[i] x b[i] ) ) with one key-switch and one rescale whatever the count
+  // (fhe_mul_sum_relin_level; 1 .. 16 terms; level 0: the lowest of the operands' levels).
+  // Operands: 2-component NTT-form ciphertexts over l_i >= level limbs, cut to `level` on the fly;
+  // they may be one object (squares, a shared factor).
+  Ciphertext mul_sum_relin(const std::vector<const Ciphertext*>& a,
+                           const std::vector<const Ciphertext*>& b, const SwitchKey& rk,
+                           bool rescale, uint32_t level = 0) const {
+    const size_t count = a.size();
+    if (count == 0 || count > 16 || b.size() != count)
+      throw Error(FHE_EINVAL, "mul_sum_relin: two lists of one length, 1 .. 16 terms");
+    std::vector<const uint64_t*> pa(count), pb(count);
+    std::vector<uint32_t> la(count), lb(count);
+    uint32_t lo = ctx_.L();
+    for (size_t i = 0; i < count; ++i) {
+      for (const Ciphertext* c : {a[i], b[i]})
+        if (!c || c->components != 2 || !c->ntt_form)
+          throw Error(FHE_EINVAL, "mul_sum_relin: need 2-component NTT-form ciphertexts");
+      pa[i] = a[i]->data(), la[i] = a[i]->limbs;
+      pb[i] = b[i]->data(), lb[i] = b[i]->limbs;
+      lo = la[i] < lo ? la[i] : lo;
+      lo = lb[i] < lo ? lb[i] : lo;
+    }
+    if (level == 0) level = lo;
+    if (level < 1 || level > ctx_.L())
+      throw Error(FHE_EINVAL, "mul_sum_relin: level must be in 1 .. L");
+    if (rescale && level < 2) throw Error(FHE_EINVAL, "mul_sum_relin: rescale needs level >= 2");
+    Ciphertext out(ctx_, 2, level - (rescale ? 1 : 0), true);
+    const size_t need = fhe_mul_relin_workspace(ctx_.get(), 1);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    check(fhe_mul_sum_relin_level(ctx_.get(), out.data(), pa.data(), la.data(), pb.data(), lb.data(),
+                                  rk.b(), rk.a(), level, (uint32_t)count, 1, rescale ? 1 : 0,
+                                  ws_.data(), s_),
+          "fhe_mul_sum_relin_level");
+    return out;
+  }
   // Divide-and-round by the last modulus: drops one limb, keeps the form.
   Ciphertext rescale(const Ciphertext& x) const {
     if (x.limbs < 2) throw Error(FHE_EINVAL, "rescale: need at least 2 limbs");
