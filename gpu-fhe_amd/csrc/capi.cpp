@@ -956,4 +956,108 @@ int fhe_decode_sparse(const fhe_ctx* c, double* slots, const uint64_t* pt, doubl
                      ws, s);
 }
 
+size_t fhe_encrypt_workspace(const fhe_ctx* c, uint32_t level, uint32_t batch) {
+  return c && level >= 1 && level <= c->L ? encrypt_workspace_bytes(c, level, batch) : 0;
+}
+
+// fhe_encrypt_level, fhe_encrypt_sk_level and fhe_encrypt_slots: a.ct, a.key, a.level, a.batch and
+// either (pt, pt_rows, pt_batch) or (slots, delta, log_slots) as the caller gave them
+static int encrypt_call(const char* who, const fhe_ctx* c, EncryptArgs a, bool slots_form,
+                        uint64_t index0, void* ws, fhe_stream_t s) {
+  const std::string w(who);
+  if (!c) {
+    set_error(w + ": null context");
+    return kInvalid;
+  }
+  if (!a.ct || !a.key) {
+    set_error(w + ": null ciphertext or key");
+    return kInvalid;
+  }
+  if (a.level == 0 || a.level > c->L) {
+    set_error(w + ": level must be in [1, L]");
+    return kInvalid;
+  }
+  if (index0 + a.batch > (1ull << 32)) {
+    set_error(w + ": index0 + batch exceeds 2^32 (the Philox counter's poly field)");
+    return kInvalid;
+  }
+  const uint64_t n = c->n;
+  const uint64_t ct_words = (uint64_t)a.batch * 2 * a.level * n;
+  if (slots_form) {
+    if (!a.slots) {
+      set_error(w + ": null slots");
+      return kInvalid;
+    }
+    if (!(std::isfinite(a.delta) && a.delta > 0)) {
+      set_error(w + ": delta must be finite and positive");
+      return kInvalid;
+    }
+    if (a.log_slots > c->log_n - 1) {
+      set_error(w + ": log_slots must be in [0, log_n - 1]");
+      return kInvalid;
+    }
+    if (spans_overlap(a.ct, ct_words, reinterpret_cast<const uint64_t*>(a.slots),
+                      (uint64_t)a.batch << (a.log_slots + 1))) {
+      set_error(w + ": ct overlaps slots");
+      return kInvalid;
+    }
+  } else {
+    if (a.pt_batch != 1 && a.pt_batch != a.batch) {
+      set_error(w + ": pt_batch must be 1 or batch");
+      return kInvalid;
+    }
+    if (a.pt && a.pt_rows < a.level) {
+      set_error(w + ": pt_rows must be at least level");
+      return kInvalid;
+    }
+    if (a.pt && spans_overlap(a.ct, ct_words, a.pt, (uint64_t)a.pt_batch * a.pt_rows * n)) {
+      set_error(w + ": ct overlaps pt");
+      return kInvalid;
+    }
+  }
+  if (spans_overlap(a.ct, ct_words, a.key, (a.secret ? c->L + c->K : 2 * (uint64_t)c->L) * n)) {
+    set_error(w + ": ct overlaps the key");
+    return kInvalid;
+  }
+  const size_t ws_bytes = encrypt_workspace_bytes(c, a.level, a.batch);
+  if (ws && spans_overlap(a.ct, ct_words, static_cast<const uint64_t*>(ws), ws_bytes / 8)) {
+    set_error(w + ": ct overlaps the workspace");
+    return kInvalid;
+  }
+  if (a.batch == 0) return kOk;
+  a.index0 = (uint32_t)index0;
+  int rc = ensure_ws(c, ws_bytes, &ws, hs(s));
+  if (rc) return rc;
+  // FHECORE_ENCRYPT_UNFUSED=1: the spread-and-whole-NTT form of wide contexts on any context;
+  // FHECORE_ENCRYPT_PASS=p: at most p ciphertexts per pass.  The same bits either way
+  // (tools/encrypt_times.py times them against the defaults)
+  const char* u = std::getenv("FHECORE_ENCRYPT_UNFUSED");
+  const char* p = std::getenv("FHECORE_ENCRYPT_PASS");
+  const long pass = p ? std::atol(p) : 0;
+  return launch_encrypt(c, a, ws, u && u[0] == '1', pass > 0 ? (uint32_t)std::min(pass, 1L << 30) : 0,
+                        hs(s));
+}
+
+int fhe_encrypt_level(const fhe_ctx* c, uint64_t* ct, const uint64_t* pt, uint32_t pt_rows,
+                      uint32_t pt_batch, const uint64_t* pk, uint32_t level, uint32_t batch,
+                      uint64_t seed, uint32_t index0, void* ws, fhe_stream_t s) {
+  EncryptArgs a{ct, pt, pt_rows, pt_batch, nullptr, 0.0, 0, pk, false, level, batch, seed, 0};
+  return encrypt_call("fhe_encrypt_level", c, a, false, index0, ws, s);
+}
+
+int fhe_encrypt_sk_level(const fhe_ctx* c, uint64_t* ct, const uint64_t* pt, uint32_t pt_rows,
+                         uint32_t pt_batch, const uint64_t* sk, uint32_t level, uint32_t batch,
+                         uint64_t seed, uint32_t index0, void* ws, fhe_stream_t s) {
+  EncryptArgs a{ct, pt, pt_rows, pt_batch, nullptr, 0.0, 0, sk, true, level, batch, seed, 0};
+  return encrypt_call("fhe_encrypt_sk_level", c, a, false, index0, ws, s);
+}
+
+int fhe_encrypt_slots(const fhe_ctx* c, uint64_t* ct, const double* slots, double delta,
+                      uint32_t log_slots, const uint64_t* key, int secret_key, uint32_t level,
+                      uint32_t batch, uint64_t seed, uint32_t index0, void* ws, fhe_stream_t s) {
+  EncryptArgs a{ct,  nullptr,         0,     1,     slots, delta, log_slots,
+                key, secret_key != 0, level, batch, seed,  0};
+  return encrypt_call("fhe_encrypt_slots", c, a, true, index0, ws, s);
+}
+
 }  // extern "C"

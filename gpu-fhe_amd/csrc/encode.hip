@@ -456,20 +456,37 @@ size_t decode_workspace_bytes(const fhe_ctx* c, u32 count) {
   return (size_t)3 * count * c->n * sizeof(u64);
 }
 
+int launch_encode_coeffs(const fhe_ctx* c, long long* cf, const double* slots, double delta,
+                         u32 log_slots, u32 count, void* work, hipStream_t s) {
+  if (count == 0) return kOk;
+  const bool full = log_slots == c->log_n - 1;
+  const double scale = delta / (double)(1ull << log_slots);
+  double2* w = static_cast<double2*>(work);
+  if (int rc = full ? launch_sfft<true>(c, slots, cf, w, scale, count, s)
+                    : launch_sfft_sparse<true>(c, slots, cf, w, scale, log_slots, count, s))
+    return rc;
+  prof_mark(s, "encode_fft");
+  return kOk;
+}
+
+int launch_encode_spread(const fhe_ctx* c, u64* out, const long long* cf, u32 rows, u32 level,
+                         u32 count, hipStream_t s) {
+  if ((u64)count * rows == 0) return kOk;
+  if (int rc = check_grid(c->n / kFftThreads, kFftThreads, rows, count, "encode")) return rc;
+  k_encode_spread<<<dim3((u32)(c->n / kFftThreads), rows, count), kFftThreads, 0, s>>>(
+      out, cf, rows, level, c->L, c->log_n, c->d_mods);
+  FHE_HIP_CHECK(hipGetLastError());
+  return kOk;
+}
+
 int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta, u32 log_slots,
                   u32 level, bool special, u32 count, void* ws, bool unfused, hipStream_t s) {
   if (count == 0) return kOk;
   const u64 n = c->n;
   const u32 rows = level + (special ? c->K : 0);
-  double2* work = static_cast<double2*>(ws);
   long long* cf = reinterpret_cast<long long*>(static_cast<u64*>(ws) + (u64)count * n);
-  const bool full = log_slots == c->log_n - 1;
-  const double scale = delta / (double)(1ull << log_slots);
   int rc;
-  if ((rc = full ? launch_sfft<true>(c, slots, cf, work, scale, count, s)
-                 : launch_sfft_sparse<true>(c, slots, cf, work, scale, log_slots, count, s)))
-    return rc;
-  prof_mark(s, "encode_fft");
+  if ((rc = launch_encode_coeffs(c, cf, slots, delta, log_slots, count, ws, s))) return rc;
   const u64 ps = (u64)rows * n;
   if (!c->wide && !unfused) {
     // the lift rides on the column-forward pass (ntt.hip k_lift_col); the row pass runs in place
@@ -481,10 +498,7 @@ int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta,
                                     c->L, c->K, s)))
       return rc;
   } else {
-    if ((rc = check_grid(n / kFftThreads, kFftThreads, rows, count, "encode"))) return rc;
-    k_encode_spread<<<dim3((u32)(n / kFftThreads), rows, count), kFftThreads, 0, s>>>(
-        out, cf, rows, level, c->L, c->log_n, c->d_mods);
-    FHE_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_encode_spread(c, out, cf, rows, level, count, s))) return rc;
     if ((rc = launch_ntt(c, true, out, out, count, ps, 0, level, s))) return rc;
     if (special && (rc = launch_ntt(c, true, out + (u64)level * n, out + (u64)level * n, count, ps,
                                     c->L, c->K, s)))

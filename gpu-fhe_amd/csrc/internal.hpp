@@ -513,11 +513,48 @@ size_t linear_transform_workspace_bytes(const fhe_ctx* c, u32 n2, u32 batch);
 int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta, u32 log_slots,
                   u32 level, bool special, u32 count, void* ws, bool unfused, hipStream_t s);
 size_t encode_workspace_bytes(const fhe_ctx* c, u32 count);
+// launch_encode's first half alone: slots -> the rounded coefficients cf [count][N] (signed words);
+// work [count][N/2] complex, touched by the two-pass sizes only
+int launch_encode_coeffs(const fhe_ctx* c, long long* cf, const double* slots, double delta,
+                         u32 log_slots, u32 count, void* work, hipStream_t s);
+// the unfused lift: cf [count][N] -> out [count][rows][N], the canonical residue of every row's limb
+// (enc_limb), coefficient form
+int launch_encode_spread(const fhe_ctx* c, u64* out, const long long* cf, u32 rows, u32 level,
+                         u32 count, hipStream_t s);
 // pt [count][pt_rows][N] NTT form (limbs 0 and, at level >= 2, 1 read) -> slots
 // [count][2^log_slots][2]; below full packing only the coefficients at the multiples of gap are read
 int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 log_slots,
                   u32 pt_rows, u32 level, u32 count, void* ws, hipStream_t s);
 size_t decode_workspace_bytes(const fhe_ctx* c, u32 count);
+
+// ---- launchers (keygen.hip): batched encryption at any level ------------------------------
+// ct [batch][2][level][N]; ciphertext i draws with poly index0 + i.  pt [pt_batch][pt_rows][N]
+// or null; slots != null: the message is encoded first (launch_encode_coeffs) and its coefficients
+// join e0 / e before the transform.  key: pk [2][L][N], or with `secret` sk [L + K][N].
+// Arguments checked by capi.cpp.
+struct EncryptArgs {
+  u64* ct;
+  const u64* pt;
+  u32 pt_rows, pt_batch;
+  const double* slots;
+  double delta;
+  u32 log_slots;
+  const u64* key;
+  bool secret;
+  u32 level, batch;
+  u64 seed;
+  u32 index0;
+};
+// A batch runs in passes of at most this many bytes of ciphertext (kKsPassBytes' size): it bounds
+// the workspace and every grid whatever the batch.  One pass or two makes no measurable difference
+// at N = 2^16, L = 16, batch 32; passes of 4 ciphertexts cost 10 %.
+constexpr size_t kEncPassBytes = 256ull << 20;
+// ciphertexts per pass; pass_override != 0 lowers it (FHECORE_ENCRYPT_PASS, capi.cpp)
+u32 encrypt_pass_batch(const fhe_ctx* c, u32 level, u32 batch, u32 pass_override);
+size_t encrypt_workspace_bytes(const fhe_ctx* c, u32 level, u32 batch);
+// unfused: the spread-and-whole-NTT form of wide contexts on any context (the same bits)
+int launch_encrypt(const fhe_ctx* c, const EncryptArgs& a, void* ws, bool unfused,
+                   u32 pass_override, hipStream_t s);
 
 // ---- launchers (pipeline.hip): SURVEY.md §8(f) row 4 -----------------------------------
 // (level: the Q-limbs of a / b, 1 .. L; the key stays the top-level one)

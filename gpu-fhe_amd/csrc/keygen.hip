@@ -36,6 +36,22 @@ __host__ __device__ inline P4 philox4x32_10(P4 c, u32 k0, u32 k1) {
 
 enum Kind : int { kUniform = 0, kTernary = 1, kError = 2 };
 
+// The draws, one definition each: (coefficient c, poly p, stream tag) under the key (k0, k1).
+// uniform mod q takes the limb's own index into the counter; a small draw is limb-free.
+__device__ __forceinline__ u64 draw_uniform(u32 c, u32 limb, u32 p, u32 tag, u32 k0, u32 k1, u64 q) {
+  const P4 r = philox4x32_10(P4{c, limb, p, tag}, k0, k1);
+  const u64 lo = ((u64)r.y << 32) | r.x, hi = ((u64)r.w << 32) | r.z;
+  const u128 t = (u128)hi * q + (u64)(((u128)lo * q) >> 64);
+  return (u64)(t >> 64);
+}
+
+__device__ __forceinline__ int64_t draw_small(int kind, u32 c, u32 p, u32 tag, u32 k0, u32 k1) {
+  const P4 r = philox4x32_10(P4{c, 0xffffffffu, p, tag}, k0, k1);
+  if (kind == kTernary) return (int64_t)(r.x % 3u) - 1;
+  const u64 bits = ((u64)r.y << 32) | r.x;
+  return (int64_t)__popcll(bits & 0x1fffffull) - (int64_t)__popcll((bits >> 21) & 0x1fffffull);
+}
+
 // out rows [poly][limb][N] (poly stride pstride) over ctx limbs limb0 + l.  Grid: x over
 // coefficients, y = limb, z = poly.  The draw for (poly, coefficient) of a small distribution does
 // not depend on the limb, so every limb holds the same integer.
@@ -50,19 +66,9 @@ __global__ __launch_bounds__(kThreads) void k_sample(u64* __restrict__ out, u64 
   const u64 q = mods[limb].q;
   u64 v;
   if (kind == kUniform) {
-    const P4 r = philox4x32_10(P4{c, limb, p, tag}, seed_lo, seed_hi);
-    const u64 lo = ((u64)r.y << 32) | r.x, hi = ((u64)r.w << 32) | r.z;
-    const u128 t = (u128)hi * q + (u64)(((u128)lo * q) >> 64);
-    v = (u64)(t >> 64);
+    v = draw_uniform(c, limb, p, tag, seed_lo, seed_hi, q);
   } else {
-    const P4 r = philox4x32_10(P4{c, 0xffffffffu, p, tag}, seed_lo, seed_hi);
-    int64_t s;
-    if (kind == kTernary) {
-      s = (int64_t)(r.x % 3u) - 1;
-    } else {
-      const u64 bits = ((u64)r.y << 32) | r.x;
-      s = (int64_t)__popcll(bits & 0x1fffffull) - (int64_t)__popcll((bits >> 21) & 0x1fffffull);
-    }
+    const int64_t s = draw_small(kind, c, p, tag, seed_lo, seed_hi);
     v = s >= 0 ? (u64)s : q - (u64)(-s);
   }
   out[(u64)p * pstride + (u64)l * n + c] = v;
@@ -119,6 +125,101 @@ int mac_s(const fhe_ctx* c, u64* out, u64 pout, const u64* x, u64 px, const u64*
 enum Tag : u32 { kTagSecret = 1, kTagPkA = 2, kTagPkE = 3, kTagSparse = 4, kTagKsA = 0x100,
                  kTagKsE = 0x101, kTagEncU = 32, kTagEncE0 = 33, kTagEncE1 = 34, kTagEncA = 35,
                  kTagEncE = 36 };
+
+// ---- batched encryption at any level (fhe_encrypt_level / _sk_level / _slots) -------------------
+// Ciphertext b of a pass is poly j = poly0 + b of the Philox counter.  Three steps:
+//   k_enc_draw    one Philox draw per (ciphertext, polynomial, coefficient), written as the signed
+//                 word the encoder's lift takes; the message's coefficients (fhe_encrypt_slots)
+//                 are added to e0 / e here, since the NTT is linear
+//   lift + NTT    launch_encode_col + launch_ntt_row_fwd_r2 (ntt.hip), or on wide contexts a spread
+//                 and whole NTTs: e0, e1 straight into ct, u (or the secret-key form's e) into
+//                 the workspace
+//   k_enc_finish  one pass over ct: in place + b u^ + pt, + a u^ (public key), or a drawn inline
+//                 as c1 and c0 = e^ - a s + pt (secret key)
+// Both kernels are shaped like k_lincomb (plain.hip): a row per blockIdx.y (its draw kind, tag,
+// ModParams uniform), a 16-byte pair per lane, rows beyond the grid's y limit by stride.
+constexpr int kEncThreads = 128;
+typedef u64 vu64x2 __attribute__((ext_vector_type(2)));
+typedef long long vi64x2 __attribute__((ext_vector_type(2)));
+
+struct EncDraw {
+  long long* u;          // [batch][N]      public-key form only
+  long long* e;          // [batch][nd - 1][N] (e0, e1), or [batch][N] (e) when nd == 1
+  const long long* msg;  // [batch][N] added into e0 / e, or null
+  u32 nd;                // draws per ciphertext: 3 (u, e0, e1) or 1 (e)
+  u32 batch, row_pairs, poly0, seed_lo, seed_hi;
+};
+
+__global__ __launch_bounds__(kEncThreads) void k_enc_draw(const EncDraw a) {
+  const u32 i = blockIdx.x * kEncThreads + threadIdx.x;
+  if (i >= a.row_pairs) return;
+  const bool pkf = a.nd == 3;
+  const u32 nrows = a.nd * a.batch;
+  for (u32 row = blockIdx.y; row < nrows; row += gridDim.y) {
+    const u32 b = row / a.nd, k = row - b * a.nd;
+    const bool is_u = pkf && k == 0;
+    const int kind = is_u ? kTernary : kError;
+    const u32 tag = pkf ? kTagEncU + k : kTagEncE;
+    long long* dst = is_u ? a.u + (u64)b * 2 * a.row_pairs
+                          : a.e + ((u64)b * (pkf ? 2 : 1) + (pkf ? k - 1 : 0)) * 2 * a.row_pairs;
+    vi64x2 r{draw_small(kind, 2 * i, a.poly0 + b, tag, a.seed_lo, a.seed_hi),
+             draw_small(kind, 2 * i + 1, a.poly0 + b, tag, a.seed_lo, a.seed_hi)};
+    if (a.msg && k == (pkf ? 1u : 0u))
+      r += __builtin_nontemporal_load(reinterpret_cast<const vi64x2*>(a.msg) +
+                                      (u64)b * a.row_pairs + i);
+    reinterpret_cast<vi64x2*>(dst)[i] = r;  // read back by the lift: a cached store
+  }
+}
+
+struct EncFinish {
+  u64* ct;          // [batch][2][level][N]; public-key form: NTT(e0), NTT(e1) on entry
+  const u64* that;  // [batch][level][N]: NTT(u), or NTT(e) of the secret-key form (ct has a row of
+                    // e per two rows of output, so that form's transform runs beside it)
+  const u64* key0;  // pk[0] = b rows, or the secret's rows     (row l at key0 + l N)
+  const u64* key1;  // pk[1] = a rows                           (public-key form)
+  const u64* pt;    // row l of ciphertext b at pt + b pt_bs + l N, or null
+  u64 pt_bs;        // 0: one plaintext for the whole batch
+  u32 level, nrows, row_pairs, poly0, seed_lo, seed_hi;
+};
+
+template <bool SK>
+__global__ __launch_bounds__(kEncThreads) void k_enc_finish(const EncFinish a,
+                                                           const ModParams* __restrict__ mods) {
+  const u32 i = blockIdx.x * kEncThreads + threadIdx.x;
+  if (i >= a.row_pairs) return;
+  for (u32 row = blockIdx.y; row < a.nrows; row += gridDim.y) {
+    const u32 b = row / a.level, l = row - b * a.level;
+    const ModParams m = mods[l];
+    const u64 roff = (u64)l * a.row_pairs + i;  // in pairs
+    vu64x2* c0 = reinterpret_cast<vu64x2*>(a.ct) + (u64)b * 2 * a.level * a.row_pairs + roff;
+    vu64x2* c1 = c0 + (u64)a.level * a.row_pairs;
+    vu64x2 p{0, 0};
+    if (a.pt) p = (reinterpret_cast<const vu64x2*>(a.pt + (u64)b * a.pt_bs) + roff)[0];
+    // the key rows serve every ciphertext: cached loads
+    const vu64x2 k0 = (reinterpret_cast<const vu64x2*>(a.key0) + roff)[0];
+    const vu64x2 t = __builtin_nontemporal_load(reinterpret_cast<const vu64x2*>(a.that) +
+                                                (u64)b * a.level * a.row_pairs + roff);
+    vu64x2 r0, r1;
+    if constexpr (SK) {
+      const vu64x2 e0 = t;
+      r1 = vu64x2{draw_uniform(2 * i, l, a.poly0 + b, kTagEncA, a.seed_lo, a.seed_hi, m.q),
+                  draw_uniform(2 * i + 1, l, a.poly0 + b, kTagEncA, a.seed_lo, a.seed_hi, m.q)};
+      const u64 t0 = mulmod_barrett(r1.x, k0.x, m), t1 = mulmod_barrett(r1.y, k0.y, m);
+      r0 = vu64x2{csub(e0.x + (t0 ? m.q - t0 : 0), m.q), csub(e0.y + (t1 ? m.q - t1 : 0), m.q)};
+    } else {
+      const vu64x2 k1 = (reinterpret_cast<const vu64x2*>(a.key1) + roff)[0];
+      const vu64x2 e0 = __builtin_nontemporal_load(c0), e1 = __builtin_nontemporal_load(c1);
+      const vu64x2 u = t;
+      r0 = vu64x2{csub(e0.x + mulmod_barrett(k0.x, u.x, m), m.q),
+                  csub(e0.y + mulmod_barrett(k0.y, u.y, m), m.q)};
+      r1 = vu64x2{csub(e1.x + mulmod_barrett(k1.x, u.x, m), m.q),
+                  csub(e1.y + mulmod_barrett(k1.y, u.y, m), m.q)};
+    }
+    r0 = vu64x2{csub(r0.x + p.x, m.q), csub(r0.y + p.y, m.q)};
+    __builtin_nontemporal_store(r0, c0);
+    __builtin_nontemporal_store(r1, c1);
+  }
+}
 
 // ---- fixed-Hamming-weight secret (fhe_keygen_secret_sparse) --------------------------------------
 // Coefficient c draws r = philox(c, 0xffffffff, 0, kTagSparse) and carries the 64-bit key
@@ -178,6 +279,124 @@ __global__ __launch_bounds__(kThreads) void k_sparse_spread(u64* __restrict__ sk
 }
 
 }  // namespace
+
+// The workspace of one pass of b ciphertexts, in words (a null base measures):
+//   draws  [3 b N]          u [b][N] then (e0, e1) [b][2][N]; the secret-key form uses e [b][N].
+//                           The encoder's FFT workspace [b][N/2] complex lives here first
+//                           (fhe_encrypt_slots): it is dead once the coefficients are written
+//   cf     [b N]            the message's coefficients (fhe_encrypt_slots)
+//   that   [b level N]      NTT(u), or NTT(e) of the secret-key form
+// One size serves the three calls: (4 + level) b N words.
+namespace {
+struct EncWs {
+  u64 *draws, *cf, *that;
+  u64 words;
+};
+EncWs enc_ws(const fhe_ctx* c, u64* base, u32 level, u32 b) {
+  WsCarve w{base};
+  EncWs r{};
+  r.draws = w.take((u64)3 * b * c->n);
+  r.cf = w.take((u64)b * c->n);
+  r.that = w.take((u64)b * level * c->n);
+  r.words = w.words;
+  return r;
+}
+}  // namespace
+
+u32 encrypt_pass_batch(const fhe_ctx* c, u32 level, u32 batch, u32 pass_override) {
+  if (batch == 0) return 0;
+  const u64 per = (u64)2 * level * c->n * sizeof(u64);
+  u64 p = std::max<u64>(1, kEncPassBytes / per);
+  if (pass_override) p = std::min<u64>(p, pass_override);
+  return (u32)std::min<u64>(batch, p);
+}
+
+size_t encrypt_workspace_bytes(const fhe_ctx* c, u32 level, u32 batch) {
+  return enc_ws(c, nullptr, level, encrypt_pass_batch(c, level, batch, 0)).words * sizeof(u64);
+}
+
+int launch_encrypt(const fhe_ctx* c, const EncryptArgs& a, void* ws, bool unfused, u32 pass_override,
+                   hipStream_t s) {
+  const u64 n = c->n;
+  const u32 level = a.level, row_pairs = (u32)(n / 2);  // N >= 2^10: whole pairs per row
+  const u32 pass = encrypt_pass_batch(c, level, a.batch, pass_override);
+  const u32 gx = (row_pairs + kEncThreads - 1) / kEncThreads;
+  const bool spread = c->wide || unfused;
+  const u64 ln = (u64)level * n;
+  int rc;
+  for (u32 i0 = 0; i0 < a.batch; i0 += pass) {
+    const u32 b = std::min(pass, a.batch - i0);
+    const EncWs w = enc_ws(c, static_cast<u64*>(ws), level, b);
+    u64* ct = a.ct + (u64)i0 * 2 * ln;
+    const long long* msg = nullptr;
+    if (a.slots) {
+      long long* cf = reinterpret_cast<long long*>(w.cf);
+      if ((rc = launch_encode_coeffs(c, cf, a.slots + ((u64)i0 << (a.log_slots + 1)), a.delta,
+                                     a.log_slots, b, w.draws, s)))
+        return rc;
+      msg = cf;
+    }
+    EncDraw d{};
+    d.u = reinterpret_cast<long long*>(w.draws);
+    d.e = reinterpret_cast<long long*>(a.secret ? w.draws : w.draws + (u64)b * n);
+    d.msg = msg;
+    d.nd = a.secret ? 1 : 3;
+    d.batch = b;
+    d.row_pairs = row_pairs;
+    d.poly0 = a.index0 + i0;
+    d.seed_lo = (u32)a.seed;
+    d.seed_hi = (u32)(a.seed >> 32);
+    const u64 drows = (u64)d.nd * b;
+    k_enc_draw<<<dim3(gx, (u32)std::min<u64>(drows, kMaxGridYZ)), kEncThreads, 0, s>>>(d);
+    FHE_HIP_CHECK(hipGetLastError());
+    prof_mark(s, "enc_draw");
+    // e0, e1 -> the rows of c0, c1 and u -> that; the secret-key form's e -> that
+    const long long* ecf = d.e;
+    const long long* tcf = a.secret ? d.e : d.u;
+    if (spread) {
+      if (!a.secret &&
+          ((rc = launch_encode_spread(c, ct, ecf, level, level, 2 * b, s)) ||
+           (rc = launch_ntt(c, true, ct, ct, 2 * b, ln, 0, level, s))))
+        return rc;
+      if ((rc = launch_encode_spread(c, w.that, tcf, level, level, b, s)) ||
+          (rc = launch_ntt(c, true, w.that, w.that, b, ln, 0, level, s)))
+        return rc;
+    } else {
+      if (!a.secret &&
+          ((rc = launch_encode_col(c, reinterpret_cast<const u64*>(ecf), ct, 2 * b, level, level,
+                                   s)) ||
+           (rc = launch_ntt_row_fwd_r2(c, ct, ln, ct, ln, 2 * b, 0, level, s))))
+        return rc;
+      if ((rc = launch_encode_col(c, reinterpret_cast<const u64*>(tcf), w.that, b, level, level,
+                                  s)) ||
+          (rc = launch_ntt_row_fwd_r2(c, w.that, ln, w.that, ln, b, 0, level, s)))
+        return rc;
+    }
+    prof_mark(s, "enc_ntt");
+    EncFinish f{};
+    f.ct = ct;
+    f.that = w.that;
+    f.key0 = a.key;
+    f.key1 = a.key + (u64)c->L * n;
+    f.pt = a.pt ? a.pt + (a.pt_batch == 1 ? 0 : (u64)i0 * a.pt_rows * n) : nullptr;
+    f.pt_bs = a.pt_batch == 1 ? 0 : (u64)a.pt_rows * n;
+    f.level = level;
+    f.nrows = b * level;  // pass <= kEncPassBytes / (2 level N words): far below 2^32
+    f.row_pairs = row_pairs;
+    f.poly0 = d.poly0;
+    f.seed_lo = d.seed_lo;
+    f.seed_hi = d.seed_hi;
+    const dim3 g(gx, std::min<u32>(f.nrows, (u32)kMaxGridYZ));
+    if (a.secret)
+      k_enc_finish<true><<<g, kEncThreads, 0, s>>>(f, c->d_mods);
+    else
+      k_enc_finish<false><<<g, kEncThreads, 0, s>>>(f, c->d_mods);
+    FHE_HIP_CHECK(hipGetLastError());
+    prof_mark(s, "enc_finish");
+  }
+  return kOk;
+}
+
 }  // namespace fhe
 
 using namespace fhe;

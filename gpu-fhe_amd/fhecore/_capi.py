@@ -130,6 +130,13 @@ SIGNATURES = {
     "fhe_encrypt": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "fhe_encrypt_sk": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "fhe_decrypt": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
+    "fhe_encrypt_workspace": (_sz, [_vp, _u32, _u32]),
+    "fhe_encrypt_level": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _u64, _u32, _vp,
+                                 _vp]),
+    "fhe_encrypt_sk_level": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _u64, _u32, _vp,
+                                    _vp]),
+    "fhe_encrypt_slots": (_i32, [_vp, _vp, _vp, ctypes.c_double, _u32, _vp, _i32, _u32, _u32,
+                                 _u64, _u32, _vp, _vp]),
     "fhe_prof_begin": (_i32, [_u32, _vp]),
     "fhe_prof_end": (_i32, [ctypes.POINTER(ctypes.c_float), _u32, ctypes.POINTER(_u32),
                             ctypes.c_char_p, _sz]),

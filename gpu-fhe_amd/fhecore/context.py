@@ -584,23 +584,108 @@ class Context:
         """Rotation key for Galois element k: switches sigma_k(s) to s."""
         return self.keygen_switch(sk, self.automorphism(sk, galois_elt, ntt_form=True), seed)
 
-    def encrypt(self, pt, pk, seed=None):
-        """Public-key encryption of an NTT-form plaintext [L, N] -> ciphertext [2, L, N]."""
-        seed = _nonce(seed)
-        ct = _empty(2, self.L, self.n, dtype=torch.int64, device=self._dev())
-        with torch.cuda.device(self.device):
-            ws = self.workspace(self.L * self.n * 8)  # a Graph keeps it (no internal workspace)
-            check(load().fhe_encrypt(self._ptr, _ptr(ct), _ptr(pt), _ptr(pk), seed, _ptr(ws),
-                                     _stream(ct)), "fhe_encrypt")
-        return ct
+    def encrypt(self, pt, pk, seed=None, *, level=None, batch=None, index0=0, workspace=None,
+                out=None):
+        """Public-key encryption of NTT-form plaintexts.  A [L, N] plaintext with no keyword
+        argument is the single top-level call (fhe_encrypt) -> [2, L, N].  Anything else is the
+        batched call (fhe_encrypt_level): pt [..., rows, N] (one plaintext per ciphertext),
+        [rows, N] with batch= (one plaintext for the whole batch) or None (zero; batch= says how
+        many), rows >= level (default: min(rows, L)) read in place -> [..., 2, level, N].
+        Ciphertext i draws with the nonce (seed, index0 + i): one seed serves a stream of batches,
+        and a (seed, index) pair must never repeat under one key (fhecore.h SECURITY note).
+        workspace: fhe_encrypt_workspace(ctx, level, batch) bytes; out must not overlap pt, the
+        key or the workspace."""
+        return self._encrypt(pt, pk, False, seed, level, batch, index0, workspace, out)
 
-    def encrypt_sk(self, pt, sk, seed=None):
+    def encrypt_sk(self, pt, sk, seed=None, *, level=None, batch=None, index0=0, workspace=None,
+                   out=None):
+        """Secret-key encryption (c1 uniform, c0 = e - c1 s + pt); the arguments of encrypt, the
+        batched call being fhe_encrypt_sk_level."""
+        return self._encrypt(pt, sk, True, seed, level, batch, index0, workspace, out)
+
+    def _encrypt(self, pt, key, secret, seed, level, batch, index0, workspace, out):
+        who = "encrypt_sk" if secret else "encrypt"
         seed = _nonce(seed)
-        ct = _empty(2, self.L, self.n, dtype=torch.int64, device=self._dev())
+        lib = load()
+        if (pt is not None and pt.dim() == 2 and pt.shape[0] == self.L and level is None and
+                batch is None and index0 == 0 and workspace is None and out is None):
+            ct = _empty(2, self.L, self.n, dtype=torch.int64, device=self._dev())
+            with torch.cuda.device(self.device):
+                if secret:
+                    check(lib.fhe_encrypt_sk(self._ptr, _ptr(ct), _ptr(pt), _ptr(key), seed,
+                                             _stream(ct)), "fhe_encrypt_sk")
+                else:
+                    ws = self.workspace(self.L * self.n * 8)  # a Graph keeps it
+                    check(lib.fhe_encrypt(self._ptr, _ptr(ct), _ptr(pt), _ptr(key), seed, _ptr(ws),
+                                          _stream(ct)), "fhe_encrypt")
+            return ct
+        _check_tensor(key, f"{who}: key", (self.n,))
+        rows, pt_batch = 0, 1
+        lead = () if batch is None else (int(batch),)
+        if pt is not None:
+            _check_tensor(pt, f"{who}: pt", (self.n,))
+            if pt.dim() < 2 or pt.device != key.device:
+                raise ValueError(f"{who}: pt must be [rows, N] or [..., rows, N] on the key's device")
+            rows = pt.shape[-2]
+            if pt.dim() > 2:
+                lead = tuple(pt.shape[:-2])
+                pt_batch = pt.numel() // (rows * self.n)
+                if batch is not None and int(batch) != pt_batch:
+                    raise ValueError(f"{who}: batch={batch} but pt holds {pt_batch} plaintexts")
+        count = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        if pt is not None and pt.dim() > 2:
+            pt_batch = count
+        if level is None:
+            level = self.L if pt is None else min(rows, self.L)
+        level = int(level)
+        if not 1 <= level <= self.L:
+            raise ValueError(f"{who}: level must be in [1, {self.L}]")
+        if not 0 <= int(index0) < 1 << 32:
+            raise ValueError(f"{who}: index0 out of range")
+        shape = (*lead, 2, level, self.n)
+        if out is None:
+            out = _empty(shape, dtype=torch.int64, device=key.device)
+        else:
+            _check_out(out, key, shape, f"{who}: out")
+        fn = lib.fhe_encrypt_sk_level if secret else lib.fhe_encrypt_level
         with torch.cuda.device(self.device):
-            check(load().fhe_encrypt_sk(self._ptr, _ptr(ct), _ptr(pt), _ptr(sk), seed, _stream(ct)),
-                  "fhe_encrypt_sk")
-        return ct
+            ws = workspace if workspace is not None else self.workspace(
+                lib.fhe_encrypt_workspace(self._ptr, level, count))
+            check(fn(self._ptr, _ptr(out), _ptr(pt), rows, pt_batch, _ptr(key), level, count, seed,
+                     int(index0), _ptr(ws), _stream(out)),
+                  "fhe_encrypt_sk_level" if secret else "fhe_encrypt_level")
+        return out
+
+    def encrypt_slots(self, z, delta, key, *, secret=False, level=None, log_slots=None, seed=None,
+                      index0=0, workspace=None, out=None):
+        """z complex128 [..., 2^log_slots] (default: N/2, full packing) -> ciphertexts
+        [..., 2, level, N] (default level: L) in one call (fhe_encrypt_slots): bit for bit
+        encrypt(encode(z, delta, level, log_slots=log_slots), key, ...) (encrypt_sk with
+        secret=True, key then being sk), without forming the plaintext: the message's coefficients
+        join the error before the transform.  seed, index0, workspace, out as encrypt."""
+        ls, ns = self._log_slots(log_slots, "encrypt_slots")
+        z = self._slots(z, "encrypt_slots", ns)
+        _check_tensor(key, "encrypt_slots: key", (self.n,))
+        seed = _nonce(seed)
+        level = self.L if level is None else int(level)
+        if not 1 <= level <= self.L:
+            raise ValueError(f"encrypt_slots: level must be in [1, {self.L}]")
+        if not 0 <= int(index0) < 1 << 32:
+            raise ValueError("encrypt_slots: index0 out of range")
+        count = z.numel() // ns
+        shape = (*z.shape[:-1], 2, level, self.n)
+        if out is None:
+            out = _empty(shape, dtype=torch.int64, device=z.device)
+        else:
+            _check_out(out, z, shape, "encrypt_slots: out")
+        lib = load()
+        with torch.cuda.device(self.device):
+            ws = workspace if workspace is not None else self.workspace(
+                lib.fhe_encrypt_workspace(self._ptr, level, count))
+            check(lib.fhe_encrypt_slots(self._ptr, _ptr(out), _ptr(z), float(delta), ls, _ptr(key),
+                                        int(bool(secret)), level, count, seed, int(index0), _ptr(ws),
+                                        _stream(out)), "fhe_encrypt_slots")
+        return out
 
     def decrypt(self, ct, sk):
         """ct [..., 2, l, N] (any level l <= L) -> plaintext c0 + c1 s [..., l, N], NTT form."""

@@ -452,7 +452,11 @@ int fhe_deserialize(const fhe_ctx* ctx, const void* host_buf, size_t size, uint6
  * and a switch key's a_j are pure functions of (seed, fixed tag), so two encryptions under one key
  * with the same seed have identical masks (their difference reveals pt1 - pt2), and two switch keys
  * generated from one seed share a_j.  Never repeat a seed per secret key: draw it from a CSPRNG or
- * a per-key monotonically increasing counter.  The explicit seed exists so tests are reproducible. */
+ * a per-key monotonically increasing counter.  The explicit seed exists so tests are reproducible.
+ * For the batched calls below (fhe_encrypt_level, fhe_encrypt_sk_level, fhe_encrypt_slots) the
+ * nonce is the pair (seed, j), j = index0 + i the ciphertext's index in the Philox counter's poly
+ * field: one seed serves a stream of up to 2^32 ciphertexts, and a (seed, j) pair must never
+ * repeat under one key.  fhe_encrypt / fhe_encrypt_sk are the pair (seed, 0). */
 int fhe_sample(const fhe_ctx* ctx, uint64_t* out, uint32_t polys, uint32_t limb0,
                uint32_t nlimbs, int kind, uint64_t seed, uint32_t tag, fhe_stream_t stream);
 int fhe_keygen_secret(const fhe_ctx* ctx, uint64_t* sk, uint64_t seed, fhe_stream_t stream);
@@ -476,6 +480,51 @@ int fhe_encrypt_sk(const fhe_ctx* ctx, uint64_t* ct, const uint64_t* pt, const u
                    uint64_t seed, fhe_stream_t stream);
 int fhe_decrypt(const fhe_ctx* ctx, uint64_t* pt, const uint64_t* ct, const uint64_t* sk,
                 uint32_t batch, uint32_t nlimbs, fhe_stream_t stream);
+
+/* ---- batched encryption at any level, from plaintexts or slots --------------------------------
+ * Everything in NTT form, canonical residues.  ct [batch][2][level][N], 1 <= level <= L.  For
+ * i < batch let j = index0 + i: the poly field of the Philox counter (oracle/pyoracle.py
+ * sample(kind, seed, tag, poly = j, ...)).
+ *   public key   pk the top-level [2][L][N], read in place at rows l < level.
+ *                u, e0, e1 = sample(ternary / error / error, seed, tags 32 / 33 / 34, poly j)
+ *                ct[i][0][l] = NTT_l(e0) + pk[0][l] NTT_l(u) + pt_i[l]
+ *                ct[i][1][l] = NTT_l(e1) + pk[1][l] NTT_l(u)
+ *   secret key   sk [L + K][N], read at rows l < level.
+ *                a[l] = sample(uniform, tag 35, poly j, limb l), drawn directly in NTT form
+ *                e    = sample(error, tag 36, poly j)
+ *                ct[i][1][l] = a[l],   ct[i][0][l] = NTT_l(e) - a[l] s[l] + pt_i[l]
+ *   plaintext    pt [pt_batch][pt_rows][N], pt_rows >= level, rows 0 .. level-1 read in place (a
+ *                top-level plaintext serves every level, as in fhe_mul_plain_level); pt_batch is 1
+ *                (one plaintext for the whole batch) or batch; pt == NULL encrypts zero.
+ *   slots        fhe_encrypt_slots is fhe_encode_sparse(slots [batch][2^log_slots][2], delta,
+ *                log_slots, level, special = 0) followed by the matching call above, bit for bit
+ *                (log_slots = log_n - 1: full packing); secret_key != 0 chooses the secret-key
+ *                form and says that `key` is sk, else pk.  The message's coefficients join e0 / e
+ *                before the transform: no plaintext is formed.
+ * Hence: element 0 of a call with index0 = 0 at level L is fhe_encrypt / fhe_encrypt_sk's result;
+ * level l gives rows 0 .. l-1 of the level-L result (small draws are limb-free, uniform draws
+ * keyed by the limb's own index); element i of a call with index0 = k is element 0 of a call with
+ * index0 = k + i, so one seed serves a stream of batches (SECURITY note above: never repeat a
+ * (seed, j) pair under one key).
+ * FHE_EINVAL before any launch: a null context, ct or key; null slots (fhe_encrypt_slots); level 0
+ * or above L; pt_rows < level with a non-null pt; pt_batch not 1 or batch; index0 + batch > 2^32; a
+ * delta that is not finite and positive; log_slots > log_n - 1; ct overlapping pt, slots, the key
+ * or the workspace passed; workspace == NULL while the stream is capturing.  batch == 0 is a
+ * no-op.  Workspace: fhe_encrypt_workspace(ctx, level, batch) bytes serve all three calls
+ * ((4 + level) N words per ciphertext of a pass; a batch runs in passes of at most 256 MiB of
+ * ciphertext); with an explicit workspace the calls are capture-safe (nothing is allocated, copied
+ * or synchronised).  Restated by tests/encrypt_ref.py. */
+size_t fhe_encrypt_workspace(const fhe_ctx* ctx, uint32_t level, uint32_t batch);
+int fhe_encrypt_level(const fhe_ctx* ctx, uint64_t* ct, const uint64_t* pt, uint32_t pt_rows,
+                      uint32_t pt_batch, const uint64_t* pk, uint32_t level, uint32_t batch,
+                      uint64_t seed, uint32_t index0, void* workspace, fhe_stream_t stream);
+int fhe_encrypt_sk_level(const fhe_ctx* ctx, uint64_t* ct, const uint64_t* pt, uint32_t pt_rows,
+                         uint32_t pt_batch, const uint64_t* sk, uint32_t level, uint32_t batch,
+                         uint64_t seed, uint32_t index0, void* workspace, fhe_stream_t stream);
+int fhe_encrypt_slots(const fhe_ctx* ctx, uint64_t* ct, const double* slots, double delta,
+                      uint32_t log_slots, const uint64_t* key, int secret_key, uint32_t level,
+                      uint32_t batch, uint64_t seed, uint32_t index0, void* workspace,
+                      fhe_stream_t stream);
 
 /* ---- fused multiply -> relinearise -> rescale ------------------------
  * a, b [batch][2][L][N] NTT form; evk_b, evk_a [dnum][L + K][N] the relinearisation key (NTT

@@ -309,6 +309,35 @@ class Evaluator {
     check(fhe_encrypt(ctx_.get(), ct.data(), pt.data(), pk.pk.data(), seed, nullptr, s_), "fhe_encrypt");
     return ct;
   }
+  // `batch` encryptions at `level` (1 .. L) in one call (fhe_encrypt_level): ciphertext i draws
+  // with the nonce (seed, index0 + i), so one seed serves a stream of batches; never repeat a
+  // (seed, index) pair under one key.  pt: one NTT-form plaintext over >= level limbs shared by
+  // the batch (a top-level one serves every level), or null for encryptions of zero.  Element 0
+  // with index0 = 0 at level L is encrypt(pt, pk, seed).
+  std::vector<Ciphertext> encrypt(const Ciphertext* pt, const PublicKey& pk, uint32_t level,
+                                  uint32_t batch, uint64_t seed, uint32_t index0 = 0) const {
+    return encrypt_batch(pt, nullptr, 0.0, 0, pk.pk.data(), false, level, batch, seed, index0);
+  }
+  // The secret-key form (fhe_encrypt_sk_level): c1 uniform, c0 = e - c1 s + pt.
+  std::vector<Ciphertext> encrypt_sk(const Ciphertext* pt, const SecretKey& sk, uint32_t level,
+                                     uint32_t batch, uint64_t seed, uint32_t index0 = 0) const {
+    return encrypt_batch(pt, nullptr, 0.0, 0, sk.s.data(), true, level, batch, seed, index0);
+  }
+  // Encode and encrypt in one call (fhe_encrypt_slots): slots holds batch x 2^log_slots complex
+  // doubles (log_slots = log_n - 1: full packing); bit for bit encode(...) then encrypt(...),
+  // without forming the plaintexts.
+  std::vector<Ciphertext> encrypt_slots(const DeviceBuffer& slots, double delta, uint32_t log_slots,
+                                        const PublicKey& pk, uint32_t level, uint32_t batch,
+                                        uint64_t seed, uint32_t index0 = 0) const {
+    return encrypt_batch(nullptr, &slots, delta, log_slots, pk.pk.data(), false, level, batch, seed,
+                         index0);
+  }
+  std::vector<Ciphertext> encrypt_slots(const DeviceBuffer& slots, double delta, uint32_t log_slots,
+                                        const SecretKey& sk, uint32_t level, uint32_t batch,
+                                        uint64_t seed, uint32_t index0 = 0) const {
+    return encrypt_batch(nullptr, &slots, delta, log_slots, sk.s.data(), true, level, batch, seed,
+                         index0);
+  }
   // c0 + c1 s over the ciphertext's limbs -> 1-component NTT-form plaintext.
   Ciphertext decrypt(const Ciphertext& ct, const SecretKey& sk) const {
     if (ct.components != 2 || !ct.ntt_form) throw Error(FHE_EINVAL, "decrypt: need an NTT-form ciphertext");
@@ -625,6 +654,43 @@ class Evaluator {
   }
 
  private:
+  std::vector<Ciphertext> encrypt_batch(const Ciphertext* pt, const DeviceBuffer* slots, double delta,
+                                        uint32_t log_slots, const uint64_t* key, bool secret,
+                                        uint32_t level, uint32_t batch, uint64_t seed,
+                                        uint32_t index0) const {
+    if (level == 0 || level > ctx_.L()) throw Error(FHE_EINVAL, "encrypt: level must be in [1, L]");
+    if (pt && (pt->components != 1 || !pt->ntt_form))
+      throw Error(FHE_EINVAL, "encrypt: need a 1-component NTT-form plaintext");
+    if (slots && (log_slots > ctx_.log_n() - 1 || slots->size() != ((size_t)batch * 2) << log_slots))
+      throw Error(FHE_EINVAL, "encrypt_slots: need batch x 2^log_slots complex slots");
+    const size_t words = (size_t)2 * level * ctx_.n();
+    DeviceBuffer all(words * (batch ? batch : 1));
+    const size_t need = fhe_encrypt_workspace(ctx_.get(), level, batch);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    if (slots)
+      check(fhe_encrypt_slots(ctx_.get(), all.data(), reinterpret_cast<const double*>(slots->data()),
+                              delta, log_slots, key, secret ? 1 : 0, level, batch, seed, index0,
+                              ws_.data(), s_),
+            "fhe_encrypt_slots");
+    else if (secret)
+      check(fhe_encrypt_sk_level(ctx_.get(), all.data(), pt ? pt->data() : nullptr,
+                                 pt ? pt->limbs : 0, 1, key, level, batch, seed, index0, ws_.data(),
+                                 s_),
+            "fhe_encrypt_sk_level");
+    else
+      check(fhe_encrypt_level(ctx_.get(), all.data(), pt ? pt->data() : nullptr, pt ? pt->limbs : 0,
+                              1, key, level, batch, seed, index0, ws_.data(), s_),
+            "fhe_encrypt_level");
+    std::vector<Ciphertext> out;
+    for (uint32_t i = 0; i < batch; ++i) {
+      out.emplace_back(ctx_, 2, level, true);
+      if (hipMemcpyAsync(out.back().data(), all.data() + i * words, words * 8,
+                         hipMemcpyDeviceToDevice, s_) != hipSuccess)
+        throw Error(FHE_EDEVICE, "encrypt: copy");
+    }
+    if (hipStreamSynchronize(s_) != hipSuccess) throw Error(FHE_EDEVICE, "encrypt: sync");
+    return out;
+  }
   uint64_t* plain_ws() const {
     const size_t need = fhe_lincomb_workspace(ctx_.get(), 1);
     if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);

@@ -104,7 +104,7 @@ def main():
         boot = bs.Bootstrapper(be, params)
         ns = n // 2 if ls is None else 1 << ls
         z = g.uniform(-1, 1, ns) + 1j * g.uniform(-1, 1, ns)
-        ct = ctx.drop_level(ctx.encrypt_sk(ctx.encode(z, delta, log_slots=ls), sk, seed=3), 1)
+        ct = ctx.encrypt_slots(z, delta, sk, secret=True, level=1, log_slots=ls, seed=3)
         runs.append(dict(ls=ls, params=params, be=be, boot=boot, z=z, ct=ct, out=None,
                          times={p: [] for p in PHASES}))
     for it in range(args.warmup + args.steps):
