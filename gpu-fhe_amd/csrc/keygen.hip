@@ -8,7 +8,7 @@
 //   uniform mod q   floor(r q / 2^128) of a 128-bit draw (bias < 2^-67 for q < 2^61)
 //   ternary         (r mod 3) - 1 of a 32-bit draw, the same integer on every limb
 //   sparse ternary  exactly h coefficients +-1: the h smallest 64-bit keys (r.x << 32) | c
-//                   (fhe_keygen_secret_sparse; restated by tests/sparse_ref.py)
+//                   (fhe_keygen_secret_sparse; restated by oracle/pyoracle.py)
 //   error           centred binomial, eta = 21 (sd ~3.2): popcount of 21 bits minus 21 bits
 // Keys and ciphertexts are NTT form over their limbs (the layout of the rest of the library).
 #include "../../include/fhecore.h"

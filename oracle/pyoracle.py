@@ -776,17 +776,126 @@ def tensor_ntt(a, b, moduli):
     return np.stack([a[0] * b[0] % qs, (a[0] * b[1] + a[1] * b[0]) % qs, a[1] * b[1] % qs])
 
 
-def mul_relin(a, b, evk_b, evk_a, qs, ps, dnum, rescale: bool, *, level=None, ntt=None):
-    """a, b (2, level, N) NTT form -> Relin(a x b) = (d0 + KS0(d2), d1 + KS1(d2)), NTT form; then
-    optionally rescale_ntt to (2, level - 1, N)."""
+def rescale_ct(x, moduli, ntt=None):
+    """rescale_ntt of both polynomials of x (2, l, N) -> (2, l - 1, N)."""
+    return np.stack([rescale_ntt(x[0], moduli, ntt), rescale_ntt(x[1], moduli, ntt)])
+
+
+def _cut(x, level):
+    """The first `level` limbs of x (..., l >= level, N), as an object array."""
+    return np.asarray(x).astype(object)[..., :level, :]
+
+
+def relin(D, evk_b, evk_a, qs, ps, dnum, rescale: bool, *, level=None, ntt=None):
+    """(D_0 + KS0(D_2), D_1 + KS1(D_2)) of a tensor (3, level, N), NTT form; then optionally
+    rescale_ct to (2, level - 1, N)."""
     ql = _live(qs, ps, level, ntt)[0]
-    d = tensor_ntt(a, b, ql)
-    ks0, ks1 = keyswitch(d[2], evk_b, evk_a, qs, ps, dnum, level=level, ntt=ntt)
+    ks0, ks1 = keyswitch(D[2], evk_b, evk_a, qs, ps, dnum, level=len(ql), ntt=ntt)
     col = _mods_col(ql)
-    out = np.stack([(d[0] + ks0) % col, (d[1] + ks1) % col])
-    if rescale:
-        out = np.stack([rescale_ntt(out[0], ql, ntt), rescale_ntt(out[1], ql, ntt)])
-    return out
+    out = np.stack([(D[0] + ks0) % col, (D[1] + ks1) % col])
+    return rescale_ct(out, ql, ntt) if rescale else out
+
+
+def mul_relin(a, b, evk_b, evk_a, qs, ps, dnum, rescale: bool, *, level=None, ntt=None):
+    """a, b (2, level, N) NTT form -> [rescale]( Relin(a x b) ), NTT form."""
+    ql = _live(qs, ps, level, ntt)[0]
+    return relin(tensor_ntt(a, b, ql), evk_b, evk_a, qs, ps, dnum, rescale, level=level, ntt=ntt)
+
+
+# ---- the sum of products with one relinearisation (fhe_mul_sum_relin_level) ----------------------
+
+def tensor_sum(As, Bs, qs, *, level=None):
+    """(D_0, D_1, D_2) = sum_i tensor_ntt(As[i] | level, Bs[i] | level) mod q_j: (3, level, N)."""
+    ql = _live(qs, [], level, None)[0]
+    col = _mods_col(ql)
+    D = 0
+    for a, b in zip(As, Bs):
+        D = (D + tensor_ntt(_cut(a, len(ql)), _cut(b, len(ql)), ql)) % col
+    return D
+
+
+def mul_sum_relin(As, Bs, evk_b, evk_a, qs, ps, dnum, rescale: bool, *, level=None, ntt=None):
+    """[rescale]( Relin( sum_i As[i] x Bs[i] ) ) at `level`: As[i], Bs[i] (2, l_i >= level, N) NTT
+    form, cut to `level` limbs.  -> (2, level, N), or (2, level - 1, N)."""
+    return relin(tensor_sum(As, Bs, qs, level=level), evk_b, evk_a, qs, ps, dnum, rescale,
+                 level=level, ntt=ntt)
+
+
+# ---- level-aware plaintext arithmetic (fhe_lincomb_level, fhe_mul_plain_level) -------------------
+
+def lincomb(cts, scalars, qs, *, level=None, const=None, rescale=False, ntt=None):
+    """sum_i scalars[i] cts[i][:, :level] (+ const on every slot of c0) mod q_j, then optionally
+    rescale_ct.  cts[i] (2, l_i >= level, N) NTT form; scalars / const Python integers (reduced
+    per limb here).  -> (2, level, N), or (2, level - 1, N)."""
+    ql = _live(qs, [], level, None)[0]
+    col = _mods_col(ql)
+    acc = np.zeros((2, len(ql), np.asarray(cts[0]).shape[-1]), dtype=object)
+    for k, ct in zip(scalars, cts):
+        acc = (acc + _cut(ct, len(ql)) * _mods_col(int(k) % q for q in ql)) % col
+    if const is not None:
+        acc[0] = (acc[0] + _mods_col(int(const) % q for q in ql)) % col
+    return rescale_ct(acc, ql, ntt) if rescale else acc
+
+
+def mul_plain(ct, pt, qs, *, level=None, rescale=False, ntt=None):
+    """ct (2, level, N) times the first `level` rows of pt (rows >= level, N), NTT form."""
+    ql = _live(qs, [], level, None)[0]
+    out = np.asarray(ct).astype(object) * _cut(pt, len(ql)) % _mods_col(ql)
+    return rescale_ct(out, ql, ntt) if rescale else out
+
+
+# ---- ModRaise (fhe_mod_raise), from its definition: for every polynomial p and limb l < out_level
+#     x = INTT_0(in[p][0])                        coefficient form, 0 <= x < q_0
+#     c = x if x <= (q_0 - 1) / 2, else x - q_0   the centred representative
+#     out[p][l] = NTT_l(c mod q_l)                canonical residues
+
+def centred_lift(ct, qs, ntt=None):
+    """ct (..., l >= 1, N) NTT form -> the centred coefficients c of limb 0, (..., N) Python
+    integers with |c| <= (q_0 - 1) / 2."""
+    q0 = int(qs[0])
+    inv = (ntt or (rns_ntt_fwd, rns_ntt_inv))[1]
+    x = np.asarray(inv(np.asarray(ct)[..., :1, :], [q0]))[..., 0, :].astype(object)
+    return np.where(x <= (q0 - 1) // 2, x, x - q0)
+
+
+def mod_raise(ct, qs, in_level, out_level, *, ntt=None):
+    """ct (..., in_level, N) NTT form, canonical residues -> (..., out_level, N)."""
+    ct = np.asarray(ct)
+    assert ct.shape[-2] == in_level and 1 <= in_level <= len(qs) and 1 <= out_level <= len(qs)
+    ql = [int(q) for q in qs[:out_level]]
+    c = centred_lift(ct, qs, ntt)
+    fwd = (ntt or (rns_ntt_fwd, rns_ntt_inv))[0]
+    return np.asarray(fwd(np.stack([c % q for q in ql], axis=-2), ql)).astype(object)
+
+
+# ---- the real / imaginary split and merge (fhe_conj_split_level / fhe_conj_merge_level) ----------
+# Defined in COEFFICIENT form so that it checks the library's NTT-domain rule (the constant
+# psi^(N/2) on the first half of a row, its negative on the second) instead of restating it:
+# X^(N/2) p is the negacyclic shift of p's coefficients by N/2,
+#     (X^(N/2) p)[i + N/2] = p[i]   (i < N/2),      (X^(N/2) p)[i - N/2] = -p[i]   (i >= N/2).
+#     split:  re = ct + cc,   im = -X^(N/2) (ct - cc)
+#     merge:  out = a + X^(N/2) b
+# Operands (..., l, N) NTT form over the first l moduli.
+
+def mul_x_half(x, ql, ntt=None):
+    """X^(N/2) x for x (..., l, N) NTT form, canonical residues -> the same."""
+    fwd, inv = ntt or (rns_ntt_fwd, rns_ntt_inv)
+    c = np.asarray(inv(np.asarray(x), ql)).astype(object)
+    h = c.shape[-1] // 2
+    return np.asarray(fwd(np.concatenate([-c[..., h:], c[..., :h]], axis=-1) % _mods_col(ql),
+                          ql)).astype(object)
+
+
+def conj_split(ct, cc, qs, *, level=None, ntt=None):
+    ql = _live(qs, [], level, None)[0]
+    col = _mods_col(ql)
+    ct, cc = np.asarray(ct).astype(object), np.asarray(cc).astype(object)
+    return (ct + cc) % col, (-mul_x_half((ct - cc) % col, ql, ntt)) % col
+
+
+def conj_merge(a, b, qs, *, level=None, ntt=None):
+    ql = _live(qs, [], level, None)[0]
+    return (np.asarray(a).astype(object) + mul_x_half(b, ql, ntt)) % _mods_col(ql)
 
 
 # ---- SURVEY.md §8(f) row 3: sampling, keys, encryption (restating csrc/keygen.hip) -------------
@@ -794,7 +903,7 @@ def mul_relin(a, b, evk_b, evk_a, qs, ps, dnum, rescale: bool, *, level=None, nt
 # SC'11 -- the Random123 construction), so each sample is a function of its coordinates.
 
 _M32 = 0xFFFFFFFF
-TAG = {"secret": 1, "pk_a": 2, "pk_e": 3, "ks_a": 0x100, "ks_e": 0x101, "enc_u": 32,
+TAG = {"secret": 1, "pk_a": 2, "pk_e": 3, "sparse": 4, "ks_a": 0x100, "ks_e": 0x101, "enc_u": 32,
        "enc_e0": 33, "enc_e1": 34, "enc_a": 35, "enc_e": 36}
 
 
@@ -836,6 +945,28 @@ def keygen_secret(seed, allm, log_n):
     n = 1 << log_n
     s = sample("ternary", seed, TAG["secret"], 0, list(enumerate(allm)), n)
     return rns_ntt_fwd(s, allm)
+
+
+def sparse_secret_coefficients(seed, h, log_n):
+    """The fixed-Hamming-weight secret of fhe_keygen_secret_sparse, from its definition:
+        r_c = philox4x32_10((c, 0xffffffff, 0, TAG["sparse"]), seed),   key_c = (r_c.x << 32) | c
+        the h coefficients with the smallest keys are nonzero: +1 if (r_c.y & 1) == 0, else -1
+    The keys are distinct (their low words are), so the set does not depend on how it is found.
+    -> int64 [N] with exactly h entries of +-1."""
+    n = 1 << log_n
+    assert 1 <= h <= n
+    k0, k1 = seed & _M32, (seed >> 32) & _M32
+    draws = [philox4x32_10((c, _M32, 0, TAG["sparse"]), k0, k1) for c in range(n)]
+    s = np.zeros(n, dtype=np.int64)
+    for c in sorted(range(n), key=lambda c: (draws[c][0] << 32) | c)[:h]:
+        s[c] = 1 if draws[c][1] & 1 == 0 else -1
+    return s
+
+
+def keygen_secret_sparse(seed, h, allm, log_n):
+    """sk [L + K][N] in NTT form, the layout of keygen_secret."""
+    s = [int(v) for v in sparse_secret_coefficients(seed, h, log_n)]
+    return rns_ntt_fwd(_to_rns(s, allm), allm)
 
 
 def keygen_public(seed, sk_ntt, qs, log_n):

@@ -1,7 +1,7 @@
 // C++ API for the bootstrap's building blocks (run by tests/test_cpp_bootstrap_ops.py on a GPU
 // box): KeyGenerator with a Hamming weight, Evaluator::conj_split and conj_merge at log_n = 10
-// compared word for word with residues the Python side computed from tests/sparse_ref.py and
-// tests/conj_ref.py, and the error codes of the three C entries.
+// compared word for word with residues the Python side computed from oracle/pyoracle.py
+// (keygen_secret_sparse, conj_split, conj_merge), and the error codes of the three C entries.
 // usage: test_bootstrap_ops FILE seed h level
 //   FILE: raw little-endian u64 words over the moduli of Context::standard(10, 4, 2, 2): the
 //   expected secret [L + K][N], then ct, cc, re, im, merge(ct, cc), each [2][level][N].

@@ -1,4 +1,4 @@
-// C++ API for batched encryption at any level (run by tests/test_cpp_encrypt.py on a GPU box):
+// C++ API for batched encryption at any level (run by tests/test_cpp_programs.py on a GPU box):
 // Evaluator::encrypt / encrypt_sk with a level and a batch and Evaluator::encrypt_slots compared
 // word for word with the C entry points (fhe_encrypt_level, fhe_encrypt_sk_level,
 // fhe_encrypt_slots), one top-level ciphertext compared with Evaluator::encrypt, the slots form

@@ -1,4 +1,4 @@
-// C++ API smoke/parity test (run by tests/test_cpp_api.py on a GPU box): Context / Evaluator from
+// C++ API smoke/parity test (run by tests/test_cpp_programs.py on a GPU box): Context / Evaluator from
 // include/fhecore.hpp against a schoolbook negacyclic product computed here with __int128.
 #include <cstdio>
 #include <random>

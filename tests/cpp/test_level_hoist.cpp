@@ -1,5 +1,5 @@
 // C++ API for the hoisted rotations and the rotation sum below the top level (run by
-// tests/test_cpp_level_hoist.py on a GPU box): a ciphertext brought from L = 4 to 2 limbs by two
+// tests/test_cpp_programs.py on a GPU box): a ciphertext brought from L = 4 to 2 limbs by two
 // Evaluator::mul_relin(rescale), then Evaluator::rotate_hoisted and Evaluator::rotate_sum at those
 // 2 limbs with the top-level keys and plaintexts, compared word for word with the C entry points
 // (fhe_rotate_hoisted_level, fhe_rotate_sum_hoisted_level).

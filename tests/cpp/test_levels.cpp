@@ -1,4 +1,4 @@
-// C++ API at levels below the top (run by tests/test_cpp_levels.py on a GPU box): two
+// C++ API at levels below the top (run by tests/test_cpp_programs.py on a GPU box): two
 // Evaluator::mul_relin(rescale) in a row, L = 3 -> 2 -> 1 limbs, and a rotation at 2 limbs, compared
 // word for word with the C entry points (fhe_mul_relin, fhe_mul_relin_level, fhe_rotate_level).
 #include <cstdio>

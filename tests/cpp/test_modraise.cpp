@@ -1,6 +1,6 @@
 // C++ API for ModRaise (run by tests/test_cpp_modraise.py on a GPU box): Evaluator::mod_raise at
 // log_n = 10 compared word for word with residues the Python side computed from
-// tests/modraise_ref.py.
+// oracle/pyoracle.py (mod_raise).
 // usage: test_modraise FILE in_level out_level
 //   FILE: raw little-endian u64 words, the input [2][in_level][N] then the expected output
 //   [2][out_level][N], over the moduli of Context::standard(10, 4, 2, 2).

@@ -1,4 +1,4 @@
-// C++ API for the sum of products with one relinearisation (run by tests/test_cpp_mulsum.py on a
+// C++ API for the sum of products with one relinearisation (run by tests/test_cpp_programs.py on a
 // GPU box): Evaluator::mul_sum_relin (mixed levels, a square, a shared operand, with and without
 // rescale) compared word for word with the C entry point fhe_mul_sum_relin_level, and one term
 // compared with Evaluator::mul_relin.

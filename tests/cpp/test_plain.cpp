@@ -1,4 +1,4 @@
-// C++ API for the plaintext arithmetic (run by tests/test_cpp_plain.py on a GPU box):
+// C++ API for the plaintext arithmetic (run by tests/test_cpp_programs.py on a GPU box):
 // Evaluator::lincomb (mixed levels, constant, rescale), mul_plain and drop_level compared word for
 // word with the C entry points (fhe_lincomb_level, fhe_mul_plain_level) and, for drop_level, with
 // the sliced host array.

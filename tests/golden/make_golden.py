@@ -32,6 +32,8 @@ ntt_N4096_L1: the O(N^2) defining sum of SURVEY.md §8a' evaluated in Python big
     reference's NTT is the identity, arithmetic.py:15-16, so it cannot pin this).
 level_refs.json (--level-refs): digests of pyoracle's key-switch family at every level; see
     level_refs below.
+op_refs.json (--op-refs): digests of the operations that joined pyoracle later and of the cases the
+    CPU and GPU tests share; see op_refs below.
 """
 import importlib
 import os
@@ -212,9 +214,39 @@ def level_refs(ops=pyoracle):
     print("wrote level_refs.json,", len(out), "digests")
 
 
+def op_refs(ops=pyoracle, **case_sources):
+    """op_refs.json: {"shape/op/level": sha256 of the uint64 result} of the plaintext-arithmetic,
+    mul-sum, ModRaise, split / merge and sparse-secret functions (tests/refs.py op_cases,
+    world_cases) on the shapes refs.PIN_OPS, and {"case/...": ...} of the five shared cases
+    (tests/cases.py case_digests).  The committed file was written before these functions were
+    pyoracle's and before tests/cases.py built the cases: `ops` was an adapter from these signatures
+    onto the five reference modules tests/ then held (which took no ntt= and ran the C transforms;
+    with the pure-Python transforms patched in they gave the same digests at log_n = 6), and
+    `case_sources` read the five setup() dicts and *_cpu() results those modules computed.  It fixes
+    what pyoracle and the case builder must compute, so regenerate it only for new cases."""
+    import json
+
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    sys.path.insert(0, os.path.join(HERE, "..", "..", "gpu-fhe_amd"))
+    import cases
+    import refs
+
+    out = {}
+    for shape in refs.PIN_OPS:
+        out.update(refs.op_digests(refs.small_world(*shape), ops, refs.c_ntt()))
+    out.update(cases.case_digests(**case_sources))
+    with open(os.path.join(HERE, "op_refs.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("wrote op_refs.json,", len(out), "digests")
+
+
 def main():
     if "--level-refs" in sys.argv:  # needs no reference checkout
         level_refs()
+        return
+    if "--op-refs" in sys.argv:
+        op_refs()
         return
     arith, poly = load_reference()
     if "--sampled-only" in sys.argv:  # only the configs[2] sampled pin (the others unchanged)

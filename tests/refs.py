@@ -131,3 +131,88 @@ def level_digests(w, ops, ntt):
             words = np.ascontiguousarray(np.asarray(f(ops, level=level, ntt=ntt), dtype=np.uint64))
             out[f"{shape}/{name}/{level}"] = hashlib.sha256(words.tobytes()).hexdigest()
     return out
+
+
+# ---- tests/golden/op_refs.json: the operations that joined pyoracle after the key-switch family ----
+# (make_golden.py --op-refs writes the digests, tests/test_op_refs_cpu.py recomputes them)
+
+PIN_OPS = PIN_SMALL + [(10, 4, 2, 2)]
+SPARSE_H = (1, 28, None)  # None: h = N
+
+
+def words(x):
+    """Python integers or int64 (signed: two's complement) -> the uint64 words that are hashed."""
+    return np.ascontiguousarray(np.asarray(np.asarray(x).astype(object) % (1 << 64), dtype=np.uint64))
+
+
+def op_cases(w, level):
+    """{name: f(ops, ntt)}: every operation of the plaintext-arithmetic, mul-sum, ModRaise and
+    split / merge families on the world w at `level`, inputs at mixed levels where the operation
+    takes them; ops is pyoracle (or anything with its signatures)."""
+    qs, ps, dnum = w["qs"], w["ps"], w["dnum"]
+    L = len(qs)
+    a, b, c = w["cts"]  # all at level L
+    up = min(level + 1, L)
+    kb, ka = w["keys"][w["ks"][1]]
+    scalars = [-(1 << 70) + 12345, (1 << 59) + 7, 1]
+    mixed = [cut(a, level), b, cut(c, up)]
+    As, Bs = [cut(a, level), b, cut(c, up), a], [b, cut(c, up), cut(c, up), cut(a, level)]
+    cases = {
+        "lincomb": lambda o, ntt: o.lincomb(mixed, scalars, qs, level=level, ntt=ntt),
+        "lincomb_const": lambda o, ntt: o.lincomb(mixed, scalars, qs, level=level,
+                                                  const=-(1 << 65) + 99, ntt=ntt),
+        "mul_plain": lambda o, ntt: o.mul_plain(cut(a, level), w["pts"][0], qs, level=level, ntt=ntt),
+        "tensor_sum": lambda o, ntt: o.tensor_sum(As, Bs, qs, level=level),
+        "relin": lambda o, ntt: o.relin(o.tensor_sum(As, Bs, qs, level=level), kb, ka, qs, ps, dnum,
+                                        False, level=level, ntt=ntt),
+        "mul_sum_relin": lambda o, ntt: o.mul_sum_relin(As, Bs, kb, ka, qs, ps, dnum, False,
+                                                        level=level, ntt=ntt),
+        "centred_lift": lambda o, ntt: o.centred_lift(cut(a, level), qs, ntt),
+        "mul_x_half": lambda o, ntt: o.mul_x_half(cut(a, level), qs[:level], ntt),
+        "conj_split": lambda o, ntt: np.stack(o.conj_split(cut(a, level), cut(b, level), qs,
+                                                           level=level, ntt=ntt)),
+        "conj_merge": lambda o, ntt: o.conj_merge(cut(a, level), cut(b, level), qs, level=level,
+                                                  ntt=ntt),
+    }
+    if level >= 2:
+        cases.update({
+            "rescale_ct": lambda o, ntt: o.rescale_ct(cut(a, level), qs[:level], ntt),
+            "lincomb_rescale": lambda o, ntt: o.lincomb(mixed, scalars, qs, level=level,
+                                                        const=-(1 << 65) + 99, rescale=True, ntt=ntt),
+            "mul_plain_rescale": lambda o, ntt: o.mul_plain(cut(a, level), w["pts"][0], qs,
+                                                            level=level, rescale=True, ntt=ntt),
+            "relin_rescale": lambda o, ntt: o.relin(o.tensor_sum(As, Bs, qs, level=level), kb, ka, qs,
+                                                    ps, dnum, True, level=level, ntt=ntt),
+            "mul_sum_relin_rescale": lambda o, ntt: o.mul_sum_relin(As, Bs, kb, ka, qs, ps, dnum,
+                                                                    True, level=level, ntt=ntt),
+        })
+    return cases
+
+
+def world_cases(w):
+    """{name: f(ops, ntt)}: the cases that are not per level.  mod_raise from level 1 and from
+    level 3 (a batch of two ciphertexts) to 1, 2 and L; the sparse secret at h = 1, 28 and N."""
+    qs, ps, log_n = w["qs"], w["ps"], w["log_n"]
+    L = len(qs)
+    both = np.stack(w["cts"][:2])
+    cases = {}
+    for i in (1, 3):
+        for o_ in (1, 2, L):
+            cases[f"mod_raise_{i}_{o_}"] = (lambda o, ntt, i=i, o_=o_:
+                                            o.mod_raise(cut(both, i), qs, i, o_, ntt=ntt))
+    for h in SPARSE_H:
+        h = h or 1 << log_n
+        cases[f"sparse_secret_coefficients_h{h}"] = (lambda o, ntt, h=h:
+                                                     o.sparse_secret_coefficients(41, h, log_n))
+        cases[f"keygen_secret_sparse_h{h}"] = (lambda o, ntt, h=h:
+                                               o.keygen_secret_sparse(41, h, qs + ps, log_n))
+    return cases
+
+
+def op_digests(w, ops, ntt):
+    """{"shape/op/level": sha256 of words(result)}; level 0 marks the cases of world_cases."""
+    L = len(w["qs"])
+    shape = f"n{w['log_n']}_L{L}_K{len(w['ps'])}_d{w['dnum']}"
+    runs = [(0, world_cases(w))] + [(level, op_cases(w, level)) for level in range(1, L + 1)]
+    return {f"{shape}/{name}/{level}": hashlib.sha256(words(f(ops, ntt)).tobytes()).hexdigest()
+            for level, cases in runs for name, f in cases.items()}

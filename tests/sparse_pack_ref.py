@@ -1,6 +1,6 @@
 """Reference for sparse packing (fhe_encode_sparse / fhe_decode_sparse, SubSum and the sparse path
 of fhecore.bootstrap): n_s = 2^log_slots slots, gap = N / (2 n_s), the message a polynomial in
-Y = X^gap.  (tests/sparse_ref.py is the sparse *secret*'s reference; this one is about packing.)
+Y = X^gap.  (pyoracle.sparse_secret_coefficients is the sparse *secret*; this is about packing.)
 
     encode   encode_ref.encode of the vector tiled gap times: an n_s-periodic slot vector has no
              coefficient off the multiples of gap, and the tiled transform's first log2(gap) stages
@@ -10,19 +10,14 @@ Y = X^gap.  (tests/sparse_ref.py is the sparse *secret*'s reference; this one is
     subsum   acc = t; acc <- acc + sigma_{5^(n_s 2^i)}(acc), i < log2(gap), on coefficient vectors
              by signed permutation: gap t[k gap] on the grid, 0 elsewhere
 
-and the case the CPU and GPU bootstrap tests share, computed once per process: bootstrap_ref's
-chain, secret and parameters at N = 2^10 with log_slots = 6 (gap 8: three SubSum steps), 64 slots
-uniform in the square encoded at bootstrap_ref's message ratio (IN_SCALE), fixed seeds, keys from
-pyoracle."""
-import functools
-import random
-
+and the parameters of the case the CPU and GPU bootstrap tests share (tests/cases.py SPARSE):
+bootstrap_ref's chain, secret and parameters at N = 2^10 with log_slots = 6 (gap 8: three SubSum
+steps), 64 slots uniform in the square encoded at bootstrap_ref's message ratio (IN_SCALE)."""
 import numpy as np
 
 import bootstrap_ref as br
 import encode_ref
 import pyoracle
-import refs
 
 LOG_SLOTS = 6
 PARAMS = dict(br.PARAMS, log_slots=LOG_SLOTS)
@@ -36,11 +31,6 @@ PARAMS = dict(br.PARAMS, log_slots=LOG_SLOTS)
 # bootstrap_ref's message ratio when it is encoded at delta / sqrt(gap); the Bootstrapper takes any
 # input scale and returns it.
 IN_SCALE = br.DELTA / float(np.sqrt(1 << (br.LOG_N - 1 - LOG_SLOTS)))
-# Maximum slot error of the sparse Bootstrapper.bootstrap on the CPU backend against the input
-# slots, measured once (deterministic under the seeds below).  At bootstrap_ref's message ratio the
-# cubic term is full packing's (cubic_term: 2.47e-5 for these slots), and the noise in front
-# of SlotToCoeff is summed over 128 coefficients and not 1024.
-SPARSE_BOOTSTRAP_ERR = 2.442e-05
 
 
 def gap(log_n, log_slots):
@@ -98,25 +88,7 @@ def cubic_term(z, delta, q0, log_slots):
     return float(np.abs(encode_ref.decode_coeffs(e, delta, log_slots + 1) - z).max())
 
 
-# ---- the CPU backend ------------------------------------------------------------------------------
-
-class CpuBackend(br.CpuBackend):
-    """bootstrap_ref.CpuBackend plus rotate, and factors given as [n2, n1, n_s] diagonals."""
-
-    def rotate(self, a, step):
-        elt = pyoracle.galois_elt(step, 1 << self.log_n)
-        kb, ka = self.rot_keys[elt]
-        return self._batched(lambda x: pyoracle.rotate(
-            x, elt, kb, ka, self.moduli, self.ps, self.dnum, self.log_n, level=x.shape[-2],
-            ntt=refs.c_ntt()), a)
-
-    def load_factor(self, z, baby, giant, delta):
-        z = np.asarray(z)
-        return super().load_factor(np.tile(z, (1 << (self.log_n - 1)) // z.shape[-1]), baby, giant,
-                                   delta)
-
-
-# ---- the shared case ------------------------------------------------------------------------------
+# ---- the shared case's rotation keys (the case itself: tests/cases.py SPARSE) ---------------------
 
 def rotation_elements(log_slots=LOG_SLOTS):
     """The Galois elements of the SubSum steps, of every baby / giant step of the six small
@@ -129,52 +101,3 @@ def rotation_elements(log_slots=LOG_SLOTS):
         for n1, n2, stride, offset in bs.factor_layouts(br.LOG_N, groups, inverse, log_slots):
             steps |= {stride * (b + offset) for b in range(n1)} | {stride * g * n1 for g in range(n2)}
     return sorted({pyoracle.galois_elt(s, n) for s in steps if s} | {2 * n - 1})
-
-
-@functools.lru_cache(maxsize=None)
-def setup():
-    """bootstrap_ref's chain, secret and relinearisation key; the sparse case's rotation keys and
-    encrypted input with seeds of their own: dict of host arrays."""
-    base = br.setup()
-    qs, ps = base["qs"], base["ps"]
-    import sparse_ref
-
-    s = [int(v) for v in sparse_ref.coefficients(br.SK_SEED, br.HAMMING, br.LOG_N)]
-    rng = random.Random(31415)
-    rot = {k: pyoracle.gen_rot_key(s, k, qs, ps, br.DNUM, rng) for k in rotation_elements()}
-    z = br.model_slots(1 << LOG_SLOTS, 11)
-    pt = encode(z, IN_SCALE, br.LOG_N, LOG_SLOTS, qs)
-    ct = pyoracle.encrypt_sk(83, pt, base["sk_ntt"], qs, br.LOG_N)
-    return dict(qs=qs, ps=ps, relin=base["relin"], rot=rot, sk_ntt=base["sk_ntt"], z=z, pt=pt,
-                ct=ct)
-
-
-def backend():
-    su = setup()
-    return CpuBackend(br.LOG_N, su["qs"], su["ps"], br.DNUM, su["relin"], su["rot"])
-
-
-def decode_case(dec, level, scale):
-    """A decrypted plaintext (level, N), NTT form -> the 64 complex slots."""
-    return decode(np.asarray(dec).astype(np.uint64), float(scale), br.LOG_N, LOG_SLOTS,
-                  setup()["qs"], level)
-
-
-def decrypt_decode(data, level, scale):
-    su = setup()
-    dec = pyoracle.decrypt(np.asarray(data).astype(object), su["sk_ntt"], su["qs"][:level])
-    return decode_case(dec, level, scale)
-
-
-@functools.lru_cache(maxsize=None)
-def bootstrap_cpu():
-    """The sparse Bootstrapper.bootstrap on the CPU backend, from the input dropped to level 1:
-    (Ct with a (2, 3, N) object array, max slot error)."""
-    from fhecore import bootstrap as bs
-    from fhecore.polyeval import Ct
-
-    su = setup()
-    boot = bs.Bootstrapper(backend(), **PARAMS)
-    out = boot.bootstrap(Ct(np.asarray(su["ct"])[:, :1], 1, IN_SCALE))
-    got = decrypt_decode(out.data, out.level, out.scale)
-    return out, float(np.abs(got - su["z"]).max())

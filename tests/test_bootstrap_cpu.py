@@ -1,29 +1,32 @@
 """fhecore.bootstrap.Bootstrapper without a GPU, on the CPU backend and the shared case of
-tests/bootstrap_ref.py: the refreshed ciphertext decrypts to the input slots, its level and scale,
-the refusals; and the self-checks of tests/sparse_ref.py, whose secret the case uses."""
+tests/cases.py (BOOTSTRAP): the refreshed ciphertext decrypts to the input slots, its level and
+scale, the refusals; and the self-checks of pyoracle.sparse_secret_coefficients, whose secret the
+case uses."""
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import bootstrap_ref as br
-import sparse_ref
+import cases
+import pyoracle
+import refs
 
 
 def test_bootstrap_decrypts_to_the_input_slots():
     """Maximum slot error of this run: 2.833e-05 (deterministic under the fixed seeds; the margin
     covers float differences between numpy builds in encode / decode only)."""
-    out, err = br.bootstrap_cpu()
+    out, err = cases.run_cpu(cases.BOOTSTRAP)
     print(f"bootstrap: level {out.level}, scale / delta {float(out.scale) / br.DELTA:.12f}, "
           f"max slot error {err:.4e}")
-    assert err < br.MARGIN * br.BOOTSTRAP_ERR
+    assert err < cases.MARGIN * cases.BOOTSTRAP_ERR
 
 
 def test_bootstrap_level_and_scale():
     from fhecore import bootstrap as bs
     from fhecore import polyeval
 
-    out, _ = br.bootstrap_cpu()
+    out, _ = cases.run_cpu(cases.BOOTSTRAP)
     assert polyeval.eval_mod_levels(31, 3) == 9
     assert out.level == br.L - 3 - 9 - 3 == br.OUT_LEVEL
     assert np.asarray(out.data).shape == (2, br.OUT_LEVEL, 1 << br.LOG_N)
@@ -31,7 +34,7 @@ def test_bootstrap_level_and_scale():
     # the result comes back at the input's scale up to the evaluator's drift (the primes sit
     # ~2^-30 off delta, three double angles)
     assert abs(out.scale / Fraction(br.DELTA) - 1) < Fraction(1, 1 << 26)
-    boot = bs.Bootstrapper(br.backend(), **br.PARAMS)
+    boot = bs.Bootstrapper(cases.backend(cases.BOOTSTRAP), **br.PARAMS)
     assert boot.out_level == br.OUT_LEVEL
     # the declared scale in front of eval_mod is delta up to the rounding of the constants' roots
     assert abs(boot.scale_cts / Fraction(br.DELTA) - 1) < Fraction(1, 1 << 48)
@@ -39,12 +42,9 @@ def test_bootstrap_level_and_scale():
 
 def test_the_raised_ciphertext_stays_inside_eval_mods_range():
     """|I| <= (h + 2) / 2 = 15 = K - 1 for the case's secret of weight 28."""
-    import modraise_ref
-    import pyoracle
-
-    su = br.setup()
+    su = cases.setup(cases.BOOTSTRAP)
     qs = su["qs"]
-    up = modraise_ref.mod_raise(np.asarray(su["ct"])[:, :1], qs, 1, 2)
+    up = pyoracle.mod_raise(np.asarray(su["ct"])[:, :1], qs, 1, 2, ntt=refs.c_ntt())
     dec = pyoracle.decrypt(up, su["sk_ntt"], qs[:2])
     import encode_ref
 
@@ -57,7 +57,7 @@ def test_the_raised_ciphertext_stays_inside_eval_mods_range():
 def test_bootstrapper_refusals():
     from fhecore import bootstrap as bs
 
-    be = br.backend()
+    be = cases.backend(cases.BOOTSTRAP)
     with pytest.raises(ValueError, match="Hamming weight"):
         bs.Bootstrapper(be, **dict(br.PARAMS, hamming_weight=29))
     with pytest.raises(ValueError, match="too short"):
@@ -69,33 +69,33 @@ def test_bootstrapper_refusals():
     assert p.hamming_weight == 2 * p.K - 4 == 28
 
 
-# ---- tests/sparse_ref.py --------------------------------------------------------------------------
+# ---- the sparse secret ----------------------------------------------------------------------------
 
 @pytest.mark.parametrize("h", [1, 28, 64, 1023, 1024])
 def test_sparse_ref_weight_is_exact(h):
-    s = sparse_ref.coefficients(5, h, 10)
+    s = pyoracle.sparse_secret_coefficients(5, h, 10)
     assert s.shape == (1024,) and set(np.unique(s)) <= {-1, 0, 1}
     assert np.count_nonzero(s) == h
 
 
 def test_sparse_ref_is_deterministic_and_seeded():
-    a, b = sparse_ref.coefficients(5, 28, 10), sparse_ref.coefficients(5, 28, 10)
+    a = pyoracle.sparse_secret_coefficients(5, 28, 10)
+    b = pyoracle.sparse_secret_coefficients(5, 28, 10)
     assert (a == b).all()
-    c = sparse_ref.coefficients(6, 28, 10)
+    c = pyoracle.sparse_secret_coefficients(6, 28, 10)
     assert (a != c).any() and (np.flatnonzero(a) != np.flatnonzero(c)).any()
     # both signs occur, and a larger weight keeps the smaller one's support (one order of keys)
     assert {-1, 1} <= set(a)
-    big = sparse_ref.coefficients(5, 64, 10)
+    big = pyoracle.sparse_secret_coefficients(5, 64, 10)
     assert (big[a != 0] == a[a != 0]).all()
 
 
 def test_sparse_ref_secret_is_the_same_integer_on_every_limb():
     import coracle
-    import pyoracle
 
     m = [int(q) for q in pyoracle.gen_moduli(10, 3)]
-    sk = sparse_ref.keygen_secret_sparse(5, 28, m, 10)
-    s = sparse_ref.coefficients(5, 28, 10)
+    sk = pyoracle.keygen_secret_sparse(5, 28, m, 10)
+    s = pyoracle.sparse_secret_coefficients(5, 28, 10)
     back = coracle.ntt_inv(np.asarray(sk).astype(np.uint64), m)
     for row, q in zip(back, m):
         assert (row == (s % q).astype(np.uint64)).all()

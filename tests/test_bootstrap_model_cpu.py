@@ -5,6 +5,7 @@ are the ones bootstrap_ref.py's choice of q_0 rests on."""
 import pytest
 
 import bootstrap_ref as br
+import cases
 
 
 # (q_0 bits, exact sine, noise) -> the model's maximum slot error at log_n = 10, seed 3
@@ -40,5 +41,5 @@ def test_the_model_at_the_shared_case():
     measured BOOTSTRAP_ERR sits on."""
     q0 = br.moduli()[0][0]
     err = br.model(br.LOG_N, float(q0), exact_sine=False)
-    print(f"model at the shared case's q_0: {err:.3e}; BOOTSTRAP_ERR {br.BOOTSTRAP_ERR:.3e}")
-    assert 0.5 * br.BOOTSTRAP_ERR < err < 2 * br.BOOTSTRAP_ERR
+    print(f"model at the shared case's q_0: {err:.3e}; BOOTSTRAP_ERR {cases.BOOTSTRAP_ERR:.3e}")
+    assert 0.5 * cases.BOOTSTRAP_ERR < err < 2 * cases.BOOTSTRAP_ERR

@@ -1,28 +1,23 @@
 """The C++ layer of the bootstrap's building blocks (include/fhecore.hpp): KeyGenerator with a
 Hamming weight, Evaluator::conj_split and conj_merge.  tests/cpp/test_bootstrap_ops.cpp compares
-them word for word with the residues computed here from tests/sparse_ref.py and tests/conj_ref.py
-and checks the three C entries' error codes."""
+them word for word with the residues computed here from pyoracle's keygen_secret_sparse, conj_split
+and conj_merge and checks the three C entries' error codes."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-import conj_ref
 import pyoracle
-import sparse_ref
+import refs
+from cpp_programs import binary, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_bootstrap_ops")
+BIN = binary("test_bootstrap_ops")
 LOG_N, L, K = 10, 4, 2  # fhe::Context::standard(10, 4, 2, 2) in the program
 
 
-def _build():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "gpu-fhe_amd"), "cpptest"], check=True)
-
-
 def test_cpp_bootstrap_ops_compiles():
-    _build()
+    build()
     assert os.access(BIN, os.X_OK)
 
 
@@ -30,15 +25,15 @@ def test_cpp_bootstrap_ops_compiles():
 @pytest.mark.parametrize("seed,h,level", [(17, 28, 3), (18, 1024, 4)])
 def test_cpp_bootstrap_ops_run_on_gpu(tmp_path, seed, h, level):
     if not os.access(BIN, os.X_OK):
-        _build()
+        build()
     m = [int(q) for q in pyoracle.gen_moduli(LOG_N, L + K)]
     qs = m[:L]
-    sk = sparse_ref.keygen_secret_sparse(seed, h, m, LOG_N)
+    sk = pyoracle.keygen_secret_sparse(seed, h, m, LOG_N)
     rng = np.random.default_rng(seed)
     ct, cc = (np.stack([rng.integers(0, q, (2, 1 << LOG_N), dtype=np.uint64) for q in qs[:level]],
                        axis=1) for _ in range(2))
-    re, im = conj_ref.conj_split(ct, cc, qs, level)
-    parts = [sk, ct, cc, re, im, conj_ref.conj_merge(ct, cc, qs, level)]
+    re, im = pyoracle.conj_split(ct, cc, qs, level=level, ntt=refs.c_ntt())
+    parts = [sk, ct, cc, re, im, pyoracle.conj_merge(ct, cc, qs, level=level, ntt=refs.c_ntt())]
     path = tmp_path / "case.bin"
     with open(path, "wb") as f:
         for p in parts:

@@ -9,19 +9,15 @@ import pytest
 
 import encode_ref
 import pyoracle
+from cpp_programs import binary, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_encode")
+BIN = binary("test_encode")
 LOG_N, L, K = 10, 4, 2  # fhe::Context::standard(10, 4, 2, 2) in the program
 DELTA = 2.0 ** 50
 
 
-def _build():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "gpu-fhe_amd"), "cpptest"], check=True)
-
-
 def test_cpp_encode_compiles():
-    _build()
+    build()
     assert os.access(BIN, os.X_OK)
 
 
@@ -29,7 +25,7 @@ def test_cpp_encode_compiles():
 @pytest.mark.parametrize("level,special", [(L, 1), (2, 0), (1, 0)])
 def test_cpp_encode_runs_on_gpu(tmp_path, level, special):
     if not os.access(BIN, os.X_OK):
-        _build()
+        build()
     allm = [int(q) for q in pyoracle.gen_moduli(LOG_N, L + K)]
     qs = [allm[i] for i in encode_ref.rows_limbs(level, bool(special), L, K)]
     rng = np.random.default_rng(29)

@@ -1,26 +1,22 @@
 """The C++ Evaluator's ModRaise (include/fhecore.hpp): tests/cpp/test_modraise.cpp raises a
 ciphertext this file wrote and compares it word for word with the residues computed here from
-tests/modraise_ref.py."""
+pyoracle.mod_raise."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-import modraise_ref
 import pyoracle
+import refs
+from cpp_programs import binary, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_modraise")
+BIN = binary("test_modraise")
 LOG_N, L, K = 10, 4, 2  # fhe::Context::standard(10, 4, 2, 2) in the program
 
 
-def _build():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "gpu-fhe_amd"), "cpptest"], check=True)
-
-
 def test_cpp_modraise_compiles():
-    _build()
+    build()
     assert os.access(BIN, os.X_OK)
 
 
@@ -28,12 +24,12 @@ def test_cpp_modraise_compiles():
 @pytest.mark.parametrize("in_level,out_level", [(1, L), (3, 2)])
 def test_cpp_modraise_runs_on_gpu(tmp_path, in_level, out_level):
     if not os.access(BIN, os.X_OK):
-        _build()
+        build()
     qs = [int(q) for q in pyoracle.gen_moduli(LOG_N, L + K)][:L]
     rng = np.random.default_rng(23)
     ct = np.stack([rng.integers(0, q, (2, 1 << LOG_N), dtype=np.uint64) for q in qs[:in_level]],
                   axis=1)
-    want = modraise_ref.mod_raise(ct, qs, in_level, out_level).astype(np.uint64)
+    want = pyoracle.mod_raise(ct, qs, in_level, out_level, ntt=refs.c_ntt()).astype(np.uint64)
     path = tmp_path / "case.bin"
     with open(path, "wb") as f:
         f.write(np.ascontiguousarray(ct).astype("<u8").tobytes())

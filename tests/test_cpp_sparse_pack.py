@@ -10,19 +10,15 @@ import pytest
 import encode_ref
 import pyoracle
 import sparse_pack_ref as sp
+from cpp_programs import binary, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_sparse_pack")
+BIN = binary("test_sparse_pack")
 LOG_N, L, K = 10, 4, 2  # fhe::Context::standard(10, 4, 2, 2) in the program
 DELTA = 2.0 ** 50
 
 
-def _build():
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "gpu-fhe_amd"), "cpptest"], check=True)
-
-
 def test_cpp_sparse_pack_compiles():
-    _build()
+    build()
     assert os.access(BIN, os.X_OK)
 
 
@@ -30,7 +26,7 @@ def test_cpp_sparse_pack_compiles():
 @pytest.mark.parametrize("ls,level,special", [(5, L, 1), (0, 2, 0), (8, 1, 0), (9, L, 0)])
 def test_cpp_sparse_pack_runs_on_gpu(tmp_path, ls, level, special):
     if not os.access(BIN, os.X_OK):
-        _build()
+        build()
     allm = [int(q) for q in pyoracle.gen_moduli(LOG_N, L + K)]
     qs = [allm[i] for i in encode_ref.rows_limbs(level, bool(special), L, K)]
     rng = np.random.default_rng(31 + ls)

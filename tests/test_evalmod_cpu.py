@@ -1,5 +1,5 @@
 """fhecore.polyeval.eval_mod without a GPU, on the CPU backend and the shared case of
-tests/evalmod_ref.py: its error against sin(2 pi K v) / (2 pi), the cap that error must respect,
+tests/cases.py (EVALMOD): its error against sin(2 pi K v) / (2 pi), the cap that error must respect,
 the distance to eps, level and scale, the refusals, and the delegation to chebyshev_eval."""
 import math
 from fractions import Fraction
@@ -7,8 +7,9 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-import evalmod_ref as er
-import plain_ref
+import cases
+
+EM = cases.EVALMOD
 
 
 def test_eval_mod_error_and_cap():
@@ -16,23 +17,23 @@ def test_eval_mod_error_and_cap():
     covers float differences between numpy builds in the decode only).  The cap
     (2 pi)^2 (2^-8)^3 / 6 = 3.9e-7 is the cubic term the choice of eps already accepts: past it
     EvalMod's own error would dominate."""
-    out, err = er.evalmod_cpu()
-    print(f"eval_mod: level {out.level}, max slot error {err:.4e}, cap {er.CAP:.4e}")
-    assert err < er.MARGIN * er.EVALMOD_ERR
-    assert err < er.CAP
-    assert abs(er.CAP - 3.9e-7) < 0.05e-7
+    out, err = cases.run_cpu(EM)
+    print(f"eval_mod: level {out.level}, max slot error {err:.4e}, cap {cases.CAP:.4e}")
+    assert err < cases.MARGIN * cases.EVALMOD_ERR
+    assert err < cases.CAP
+    assert abs(cases.CAP - 3.9e-7) < 0.05e-7
 
 
 def test_eval_mod_removes_the_integer_part():
     """K v = I + eps: the result is eps within the cubic term plus the measured error."""
-    out, err = er.evalmod_cpu()
-    su = er.setup()
-    got = er.decrypt_decode(out.data, out.level, out.scale)
+    out, err = cases.run_cpu(EM)
+    su = cases.setup(EM)
+    got = cases.decrypt_decode(EM, out.data, out.level, out.scale)
     dist = float(np.abs(got - su["eps"]).max())
     print(f"eval_mod: max distance to eps {dist:.4e}")
-    assert dist <= er.CAP + er.MARGIN * er.EVALMOD_ERR
-    assert np.abs(su["v"] * er.K - np.round(su["v"] * er.K)).max() <= er.EPS_MAX
-    assert np.abs(np.round(su["v"] * er.K)).max() == er.K - 1  # the whole range of I is used
+    assert dist <= cases.CAP + cases.MARGIN * cases.EVALMOD_ERR
+    assert np.abs(su["v"] * cases.K - np.round(su["v"] * cases.K)).max() <= cases.EPS_MAX
+    assert np.abs(np.round(su["v"] * cases.K)).max() == cases.K - 1  # the whole range of I is used
 
 
 def test_eval_mod_level_and_scale():
@@ -40,13 +41,13 @@ def test_eval_mod_level_and_scale():
 
     assert polyeval.eval_mod_levels(31, 3) == 9
     assert polyeval.eval_mod_levels(31, 0) == polyeval.levels_needed(31) == 6
-    out, _ = er.evalmod_cpu()
-    assert out.level == er.L - 9 == 3
-    assert np.asarray(out.data).shape == (2, 3, 1 << er.LOG_N)
+    out, _ = cases.run_cpu(EM)
+    assert out.level == EM.L - 9 == 3
+    assert np.asarray(out.data).shape == (2, 3, 1 << EM.log_n)
     # the scale: chebyshev_eval ends at exactly delta; each double angle squares the scale and
     # divides by the prime it rescales by; then the factor 1 / (2 pi) as the float 2 pi
-    qs = er.setup()["qs"]
-    s = Fraction(er.DELTA)
+    qs = cases.setup(EM)["qs"]
+    s = Fraction(EM.delta)
     for level in (6, 5, 4):  # the levels of the three products' inputs
         s = s * s / qs[level - 1]
     assert out.scale == s * Fraction(2.0 * math.pi)
@@ -55,16 +56,16 @@ def test_eval_mod_level_and_scale():
 def test_eval_mod_refusals():
     from fhecore import polyeval
 
-    su = er.setup()
-    be = er.backend()
+    su = cases.setup(EM)
+    be = cases.backend(EM)
     # 9 levels consumed and one must remain: an input at level 9 is too low (nothing is computed)
     with pytest.raises(ValueError, match="too few levels"):
-        polyeval.eval_mod(be, polyeval.Ct(su["ct"][:, :9], 9, er.DELTA), er.K, er.DEGREE,
-                          er.DOUBLE_ANGLES)
+        polyeval.eval_mod(be, polyeval.Ct(su["ct"][:, :9], 9, EM.delta), cases.K, cases.DEGREE,
+                          cases.DOUBLE_ANGLES)
     with pytest.raises(ValueError, match="K"):
-        polyeval.eval_mod(be, polyeval.Ct(su["ct"], er.L, er.DELTA), 0)
+        polyeval.eval_mod(be, polyeval.Ct(su["ct"], EM.L, EM.delta), 0)
     with pytest.raises(ValueError, match="degree"):  # chebyshev_eval's own error
-        polyeval.eval_mod(be, polyeval.Ct(su["ct"], er.L, er.DELTA), er.K, degree=64)
+        polyeval.eval_mod(be, polyeval.Ct(su["ct"], EM.L, EM.delta), cases.K, degree=64)
 
 
 def test_eval_mod_without_double_angles_is_chebyshev_eval():
@@ -72,9 +73,9 @@ def test_eval_mod_without_double_angles_is_chebyshev_eval():
     bit for bit, with the declared scale times 2 pi."""
     from fhecore import polyeval
 
-    su = er.setup()
-    be = er.backend()
-    ct = polyeval.Ct(su["ct"][:, :4], 4, er.DELTA)
+    su = cases.setup(EM)
+    be = cases.backend(EM)
+    ct = polyeval.Ct(su["ct"][:, :4], 4, EM.delta)
     got = polyeval.eval_mod(be, ct, 1, degree=3, double_angles=0)
     c = np.polynomial.chebyshev.chebinterpolate(
         lambda v: np.cos((2.0 * math.pi * 1 * v - math.pi / 2) / 1.0), 3)

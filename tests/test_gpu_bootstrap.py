@@ -1,10 +1,11 @@
-"""fhecore.bootstrap.Bootstrapper on the GPU backend: the shared case of tests/bootstrap_ref.py bit
+"""fhecore.bootstrap.Bootstrapper on the GPU backend: the shared case of tests/cases.py (BOOTSTRAP) bit
 for bit against the CPU backend, then the same slots under keys made on the device with a secret
 of Hamming weight 28, from a ciphertext dropped to level 1, and a second bootstrap of the result."""
 import numpy as np
 import pytest
 
 import bootstrap_ref as br
+import cases
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +19,7 @@ def fc():
 
 @pytest.fixture(scope="module")
 def ctx(fc):
-    su = br.setup()
+    su = cases.setup(cases.BOOTSTRAP)
     c = fc.Context(br.LOG_N, moduli=su["qs"], special=su["ps"], dnum=br.DNUM)
     assert c.moduli == su["qs"] and c.special == su["ps"]
     return c
@@ -34,16 +35,16 @@ def test_bootstrap_matches_the_cpu_backend_bit_for_bit(fc, ctx):
     from fhecore import bootstrap as bs
     from fhecore.polyeval import Ct
 
-    su = br.setup()
+    su = cases.setup(cases.BOOTSTRAP)
     d = lambda key: (fc.to_device(u64(key[0])), fc.to_device(u64(key[1])))  # noqa: E731
     be = bs.GpuBackend(ctx, relin_key=d(su["relin"]), rot_keys={k: d(v) for k, v in su["rot"].items()})
     boot = bs.Bootstrapper(be, **br.PARAMS)
     ct = fc.to_device(u64(np.asarray(su["ct"])[:, :1]))
     out = boot.bootstrap(Ct(ct, 1, br.DELTA))
-    ref, err = br.bootstrap_cpu()
+    ref, err = cases.run_cpu(cases.BOOTSTRAP)
     assert (out.level, out.scale) == (ref.level, ref.scale)
     assert (fc.to_host(out.data) == u64(ref.data)).all()
-    assert err < br.MARGIN * br.BOOTSTRAP_ERR
+    assert err < cases.MARGIN * cases.BOOTSTRAP_ERR
 
 
 def test_bootstrap_under_device_keys(fc, ctx):
@@ -56,7 +57,7 @@ def test_bootstrap_under_device_keys(fc, ctx):
     from fhecore import bootstrap as bs
     from fhecore.polyeval import Ct
 
-    su = br.setup()
+    su = cases.setup(cases.BOOTSTRAP)
     sk = ctx.keygen_secret(seed=51, hamming_weight=br.HAMMING)
     be = bs.GpuBackend(ctx, sk=sk, seed=1000)
     boot = bs.Bootstrapper(be, **br.PARAMS)
@@ -68,17 +69,17 @@ def test_bootstrap_under_device_keys(fc, ctx):
     assert tuple(out.data.shape) == (2, br.OUT_LEVEL, 1 << br.LOG_N)
 
     def slots(c):
-        return br.decode(fc.to_host(ctx.decrypt(c.data, sk)), c.level, c.scale)
+        return cases.decode(cases.BOOTSTRAP, fc.to_host(ctx.decrypt(c.data, sk)), c.level, c.scale)
 
     err = float(np.abs(slots(out) - su["z"]).max())
     print(f"bootstrap under device keys: max slot error {err:.4e} "
-          f"(CPU run {br.BOOTSTRAP_ERR:.4e}), scale / delta {float(out.scale) / br.DELTA:.12f}")
-    assert err < 2 * br.BOOTSTRAP_ERR
+          f"(CPU run {cases.BOOTSTRAP_ERR:.4e}), scale / delta {float(out.scale) / br.DELTA:.12f}")
+    assert err < 2 * cases.BOOTSTRAP_ERR
     again = boot.bootstrap(out)
     assert again.level == br.OUT_LEVEL
     err2 = float(np.abs(slots(again) - su["z"]).max())
     print(f"second bootstrap: max slot error {err2:.4e}")
-    assert err2 < 4 * br.BOOTSTRAP_ERR
+    assert err2 < 4 * cases.BOOTSTRAP_ERR
 
 
 def test_encode_strided_diagonals_matches_the_backend_encoding(fc, ctx):

@@ -1,5 +1,5 @@
-"""fhe_conj_split_level / fhe_conj_merge_level on the GPU (csrc/plain.hip) against
-tests/conj_ref.py, which multiplies by X^(N/2) in coefficient form: bit for bit at every level,
+"""fhe_conj_split_level / fhe_conj_merge_level on the GPU (csrc/plain.hip) against pyoracle's
+conj_split / conj_merge, which multiply by X^(N/2) in coefficient form: bit for bit at every level,
 batch 1 and 3 (the batch / limb strides and the k = N/2 sign boundary), 50-, 60- and 62-bit chains;
 in place, the refused overlaps, the slots under device keys, and inside a captured Graph."""
 import ctypes
@@ -7,9 +7,11 @@ import ctypes
 import numpy as np
 import pytest
 
-import conj_ref
+import pyoracle
+import refs
 
 pytestmark = pytest.mark.gpu
+NTT = refs.c_ntt()
 
 LOG_N, L, K, DNUM = 10, 3, 1, 3
 N = 1 << LOG_N
@@ -53,12 +55,12 @@ def test_split_and_merge_match_the_coefficient_form_reference(fc, bits, batch, l
     b[0, 1, :, N // 2 - 1:N // 2 + 1] = 0
     da, db = fc.to_device(a), fc.to_device(b)
     re, im = ctx.conj_split(da, db)
-    want_re, want_im = conj_ref.conj_split(a, b, qs, level)
+    want_re, want_im = pyoracle.conj_split(a, b, qs, level=level, ntt=NTT)
     assert tuple(re.shape) == tuple(im.shape) == (batch, 2, level, N)
     assert (fc.to_host(re) == u64(want_re)).all()
     assert (fc.to_host(im) == u64(want_im)).all()
     out = ctx.conj_merge(da, db)
-    assert (fc.to_host(out) == u64(conj_ref.conj_merge(a, b, qs, level))).all()
+    assert (fc.to_host(out) == u64(pyoracle.conj_merge(a, b, qs, level=level, ntt=NTT))).all()
     # the inputs are untouched
     assert (fc.to_host(da) == a).all() and (fc.to_host(db) == b).all()
 
@@ -67,7 +69,7 @@ def test_unbatched_operands(fc):
     ctx = ctx_for(fc, 60)
     a, b = rand(ctx.moduli[:2], (2,), 1), rand(ctx.moduli[:2], (2,), 2)
     re, im = ctx.conj_split(fc.to_device(a), fc.to_device(b))
-    want = conj_ref.conj_split(a, b, ctx.moduli, 2)
+    want = pyoracle.conj_split(a, b, ctx.moduli, level=2, ntt=NTT)
     assert tuple(re.shape) == (2, 2, N)
     assert (fc.to_host(re) == u64(want[0])).all() and (fc.to_host(im) == u64(want[1])).all()
 
@@ -77,7 +79,7 @@ def test_in_place(fc, bits):
     ctx = ctx_for(fc, bits)
     qs = ctx.moduli
     a, b = rand(qs, (3, 2), 5), rand(qs, (3, 2), 6)
-    want_re, want_im = conj_ref.conj_split(a, b, qs, L)
+    want_re, want_im = pyoracle.conj_split(a, b, qs, level=L, ntt=NTT)
     da, db = fc.to_device(a), fc.to_device(b)
     re, im = ctx.conj_split(da, db, out=(da, db))  # re is ct, im is cc
     assert re is da and im is db
@@ -87,10 +89,10 @@ def test_in_place(fc, bits):
     assert (fc.to_host(db) == u64(want_re)).all() and (fc.to_host(da) == u64(want_im)).all()
     da, db = fc.to_device(a), fc.to_device(b)
     assert ctx.conj_merge(da, db, out=da) is da  # out is a
-    assert (fc.to_host(da) == u64(conj_ref.conj_merge(a, b, qs, L))).all()
+    assert (fc.to_host(da) == u64(pyoracle.conj_merge(a, b, qs, level=L, ntt=NTT))).all()
     da = fc.to_device(a)
     ctx.conj_merge(da, db, out=db)  # out is b
-    assert (fc.to_host(db) == u64(conj_ref.conj_merge(a, b, qs, L))).all()
+    assert (fc.to_host(db) == u64(pyoracle.conj_merge(a, b, qs, level=L, ntt=NTT))).all()
 
 
 def test_overlaps_and_bad_arguments_are_refused(fc):
@@ -185,6 +187,6 @@ def test_graph_replay_without_a_workspace(fc):
         g.launch()
         g.launch()
     stream.synchronize()
-    want_re, want_im = conj_ref.conj_split(a, b, qs, 2)
+    want_re, want_im = pyoracle.conj_split(a, b, qs, level=2, ntt=NTT)
     assert (fc.to_host(re) == u64(want_re)).all() and (fc.to_host(im) == u64(want_im)).all()
-    assert (fc.to_host(out) == u64(conj_ref.conj_merge(want_re, want_im, qs, 2))).all()
+    assert (fc.to_host(out) == u64(pyoracle.conj_merge(want_re, want_im, qs, level=2, ntt=NTT))).all()

@@ -1,10 +1,12 @@
-"""fhecore.polyeval.eval_mod on the GPU backend: the shared case of tests/evalmod_ref.py bit for
+"""fhecore.polyeval.eval_mod on the GPU backend: the shared case of tests/cases.py (EVALMOD) bit for
 bit against the CPU backend, and the same slots under keys made on the device, next to a
 mod_raise of the ciphertext from the bottom of the chain."""
 import numpy as np
 import pytest
 
-import evalmod_ref as er
+import cases
+
+EM = cases.EVALMOD
 
 pytestmark = pytest.mark.gpu
 
@@ -18,8 +20,8 @@ def fc():
 
 @pytest.fixture(scope="module")
 def ctx(fc):
-    su = er.setup()
-    c = fc.Context(er.LOG_N, moduli=su["qs"], special=su["ps"], dnum=er.DNUM)
+    su = cases.setup(EM)
+    c = fc.Context(EM.log_n, moduli=su["qs"], special=su["ps"], dnum=EM.dnum)
     assert c.moduli == su["qs"] and c.special == su["ps"]
     return c
 
@@ -32,15 +34,15 @@ def test_eval_mod_matches_the_cpu_backend_bit_for_bit(fc, ctx):
     """Both backends receive the same integer scalars, so data, level and scale are the same."""
     from fhecore import polyeval
 
-    su = er.setup()
-    key = (fc.to_device(u64(su["evk_b"])), fc.to_device(u64(su["evk_a"])))
+    su = cases.setup(EM)
+    key = (fc.to_device(u64(su["relin"][0])), fc.to_device(u64(su["relin"][1])))
     be = polyeval.GpuBackend(ctx, key)
-    ct = polyeval.Ct(fc.to_device(u64(su["ct"])), er.L, er.DELTA)
-    out = polyeval.eval_mod(be, ct, er.K, er.DEGREE, er.DOUBLE_ANGLES)
-    ref, err = er.evalmod_cpu()
+    ct = polyeval.Ct(fc.to_device(u64(su["ct"])), EM.L, EM.delta)
+    out = polyeval.eval_mod(be, ct, cases.K, cases.DEGREE, cases.DOUBLE_ANGLES)
+    ref, err = cases.run_cpu(EM)
     assert (out.level, out.scale) == (ref.level, ref.scale)
     assert (fc.to_host(out.data) == u64(ref.data)).all()
-    assert err < er.MARGIN * er.EVALMOD_ERR
+    assert err < cases.MARGIN * cases.EVALMOD_ERR
 
 
 def test_eval_mod_under_device_keys(fc, ctx):
@@ -49,19 +51,19 @@ def test_eval_mod_under_device_keys(fc, ctx):
     encryption of the shared slots decrypts and decodes within the constant of the CPU run."""
     from fhecore import polyeval
 
-    su = er.setup()
+    su = cases.setup(EM)
     sk = ctx.keygen_secret(seed=21)
     key = ctx.keygen_relin(sk, seed=22)
     ct = ctx.encrypt_sk(fc.to_device(su["pt"]), sk, seed=23)
     up = ctx.mod_raise(ctx.drop_level(ct, 1))
-    assert tuple(up.shape) == (2, er.L, 1 << er.LOG_N)
+    assert tuple(up.shape) == (2, EM.L, 1 << EM.log_n)
     assert (up[:, 0] == ct[:, 0]).all()
-    out = polyeval.eval_mod(polyeval.GpuBackend(ctx, key), polyeval.Ct(ct, er.L, er.DELTA), er.K,
-                            er.DEGREE, er.DOUBLE_ANGLES)
+    out = polyeval.eval_mod(polyeval.GpuBackend(ctx, key), polyeval.Ct(ct, EM.L, EM.delta), cases.K,
+                            cases.DEGREE, cases.DOUBLE_ANGLES)
     assert out.level == 3
-    got = er.decode(fc.to_host(ctx.decrypt(out.data, sk)), out.level, out.scale)
-    err = float(np.abs(got - er.target(su["v"])).max())
+    got = cases.decode(EM, fc.to_host(ctx.decrypt(out.data, sk)), out.level, out.scale)
+    err = float(np.abs(got - cases.evalmod_target(su["v"])).max())
     print(f"eval_mod under device keys: max slot error {err:.4e} "
-          f"(CPU run {er.EVALMOD_ERR:.4e}, cap {er.CAP:.4e})")
-    assert err < er.MARGIN * er.EVALMOD_ERR
-    assert float(np.abs(got - su["eps"]).max()) <= er.CAP + er.MARGIN * er.EVALMOD_ERR
+          f"(CPU run {cases.EVALMOD_ERR:.4e}, cap {cases.CAP:.4e})")
+    assert err < cases.MARGIN * cases.EVALMOD_ERR
+    assert float(np.abs(got - su["eps"]).max()) <= cases.CAP + cases.MARGIN * cases.EVALMOD_ERR

@@ -1,4 +1,4 @@
-"""GPU parity for ModRaise (fhe_mod_raise; include/fhecore.h) against tests/modraise_ref.py, bit for
+"""GPU parity for ModRaise (fhe_mod_raise; include/fhecore.h) against pyoracle.mod_raise, bit for
 bit: 60-, 61- and 62-bit chains (the last takes the unfused path of wide contexts), a second N, a
 60-bit q_0 over 50-bit primes, both workgroup placements, strided inputs, every boundary of the
 centring, the refusals, graph capture, the m + q_0 I identity under real keys on the device, and
@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 import coracle
-import modraise_ref
 import pyoracle
+import refs
 
 pytestmark = pytest.mark.gpu
 
@@ -78,7 +78,7 @@ def test_mod_raise_matches_the_reference(fc, log_n, L, K, dnum, bits):
         assert all(q < qs[0] // 2 for q in qs[1:])
     n = 1 << log_n
     full = boundary_input(qs, log_n, 4, seed=41)
-    want = u64(modraise_ref.mod_raise(full[:, :, :1], qs, 1, L))  # [4][2][L][N]
+    want = u64(pyoracle.mod_raise(full[:, :, :1], qs, 1, L, ntt=refs.c_ntt()))  # [4][2][L][N]
     assert (want[:, :, 0] == full[:, :, 0]).all()
     for batch in (1, 3, 4):
         for in_level in (1, L):
@@ -151,7 +151,7 @@ def test_graph_replay(fc):
     n = 1 << log_n
     lib = fc.load()
     ins = [boundary_input(qs, log_n, 2, seed=s)[:, :, :2].copy() for s in (47, 48)]
-    wants = [u64(modraise_ref.mod_raise(h, qs, 2, L)) for h in ins]
+    wants = [u64(pyoracle.mod_raise(h, qs, 2, L, ntt=refs.c_ntt())) for h in ins]
     x = fc.to_device(ins[0])
     ws = ctx.workspace(lib.fhe_mod_raise_workspace(ctx.handle, 2))
     out = torch.zeros(2, 2, L, n, dtype=torch.int64, device=x.device)

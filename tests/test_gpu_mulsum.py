@@ -1,5 +1,5 @@
 """GPU parity for the sum of ciphertext products with one relinearisation
-(fhe_mul_sum_relin_level; include/fhecore.h) against tests/mulsum_ref.py, bit for bit: every count
+(fhe_mul_sum_relin_level; include/fhecore.h) against pyoracle.mul_sum_relin, bit for bit: every count
 that fills, overflows or underfills a term group, every level of contexts on each key-switch path
 (fused lz16, alpha = 4, unfused dnum > 4, a 61-bit chain, a wide 62-bit chain), mixed input levels,
 aliased operands, the accumulators at their bound, both workspaces, a captured graph, every
@@ -10,7 +10,11 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-import mulsum_ref
+import cases
+import pyoracle
+import refs
+
+MS = cases.MULSUM
 
 pytestmark = pytest.mark.gpu
 
@@ -93,9 +97,9 @@ def reference(w, As, Bs, level, batch=None):
     """[(plain, rescaled or None)] per ciphertext of the batch: As[i], Bs[i] host [BATCH, 2, l, N]."""
     out = []
     for c in range(batch or As[0].shape[0]):
-        r = mulsum_ref.mul_sum_relin([a[c] for a in As], [b[c] for b in Bs], w["kb"], w["ka"],
-                                     w["qs"], w["ps"], w["dnum"], level, False)
-        out.append((r, mulsum_ref.rescaled(r, w["qs"], level) if level >= 2 else None))
+        r = pyoracle.mul_sum_relin([a[c] for a in As], [b[c] for b in Bs], w["kb"], w["ka"], w["qs"],
+                                   w["ps"], w["dnum"], False, level=level, ntt=refs.c_ntt())
+        out.append((r, pyoracle.rescale_ct(r, w["qs"][:level], refs.c_ntt()) if level >= 2 else None))
     return out
 
 
@@ -198,7 +202,7 @@ def test_structured_inputs(fc, bits):
     dtop = d(top)
     for level in (1, 2, L):
         want = reference(w, [top] * 16, [top] * 16, level)
-        D = mulsum_ref.tensor_sum([top[0]] * 16, [top[0]] * 16, w["qs"], level)
+        D = pyoracle.tensor_sum([top[0]] * 16, [top[0]] * 16, w["qs"], level=level)
         assert [int(D[k, 0, 0]) for k in range(3)] == [16, 32, 16]
         for rescale in (False, True) if level >= 2 else (False,):
             got = ctx.mul_sum_relin([dtop] * 16, [dtop] * 16, w["dkb"], w["dka"], rescale=rescale,
@@ -209,7 +213,7 @@ def test_structured_inputs(fc, bits):
         z[:, 1] = 0
     Bs = w["pool"][3:8]
     for level in (1, L):
-        D = mulsum_ref.tensor_sum([z[0] for z in zero], [b[0] for b in Bs], w["qs"], level)
+        D = pyoracle.tensor_sum([z[0] for z in zero], [b[0] for b in Bs], w["qs"], level=level)
         assert not D[2].any() and D[0].any() and D[1].any()
         want = reference(w, zero, Bs, level)
         got = ctx.mul_sum_relin([d(z) for z in zero], w["dpool"][3:8], w["dkb"], w["dka"],
@@ -377,35 +381,34 @@ def test_full_size_call_across_a_pass(fc):
 
 # ---- the shared decrypt case -----------------------------------------------------------------------
 
-@pytest.mark.parametrize("count", mulsum_ref.COUNTS)
+@pytest.mark.parametrize("count", cases.COUNTS)
 def test_inner_product_decrypts(fc, count):
     """polyeval.inner_product on the GPU backend equals the CPU backend bit for bit, decrypts to
     numpy's sum_i z_i w_i with no more error than the composed form (mul_relin(rescale) per term,
     then the sum, evaluated here on the device), and within 1.5x of the recorded constant."""
     from fhecore import polyeval
 
-    r = mulsum_ref
-    su = r.setup()
-    ctx = ctx_for(fc, r.LOG_N, r.L, r.K, r.DNUM, r.BITS)
+    su = cases.setup(MS)
+    ctx = ctx_for(fc, MS.log_n, MS.L, MS.nspecial, MS.dnum, MS.bits)
     assert ctx.moduli == su["qs"]
     d = fc.to_device
-    be = polyeval.GpuBackend(ctx, (d(su["evk_b"]), d(su["evk_a"])))
-    xs, ys = r.operands(count, wrap=d)
+    be = polyeval.GpuBackend(ctx, tuple(d(np.asarray(k, dtype=np.uint64)) for k in su["relin"]))
+    xs, ys = cases.mulsum_operands(count, wrap=d)
     out = polyeval.inner_product(be, xs, ys)
-    cpu, cpu_err = r.fused_cpu(count)
-    assert out.level == cpu.level == r.L - 1 and out.scale == cpu.scale
+    cpu, cpu_err = cases.run_cpu(MS, count)
+    assert out.level == cpu.level == MS.L - 1 and out.scale == cpu.scale
     host = fc.to_host(out.data)
     assert (host.astype(object) == cpu.data).all()
-    err = r.slot_error(polyeval.Ct(host, out.level, out.scale), count)
+    err = cases.slot_error(MS, polyeval.Ct(host, out.level, out.scale), count)
     # the composed form on the device: one mul_relin(rescale) per term, then their sum
     acc = None
     for x, y in zip(xs, ys):
         p = be.mul_relin(x.data, y.data, True)
         acc = p if acc is None else ctx.vec("add", acc, p)
-    composed = polyeval.Ct(fc.to_host(acc), r.L - 1, Fraction(r.DELTA) ** 2 / su["qs"][r.L - 1])
-    ref_err = r.slot_error(composed, count)
+    composed = polyeval.Ct(fc.to_host(acc), MS.L - 1, Fraction(MS.delta) ** 2 / su["qs"][MS.L - 1])
+    ref_err = cases.slot_error(MS, composed, count)
     print(f"count {count}: fused max slot error {err:.3e}, composed {ref_err:.3e} "
-          f"(recorded {r.FUSED_ERR[count]:.3e} / {r.COMPOSED_ERR[count]:.3e})")
+          f"(recorded {cases.FUSED_ERR[count]:.3e} / {cases.COMPOSED_ERR[count]:.3e})")
     assert err == cpu_err
     assert err <= ref_err
-    assert err < 1.5 * r.FUSED_ERR[count]
+    assert err < 1.5 * cases.FUSED_ERR[count]

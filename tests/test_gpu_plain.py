@@ -1,7 +1,7 @@
 """GPU parity for the level-aware plaintext arithmetic (fhe_lincomb_level, fhe_mul_plain_level;
-include/fhecore.h) against tests/plain_ref.py, bit for bit: every output level, mixed input levels,
-1 .. 16 terms, the constant, the fused rescale, the worst-case accumulation on 60-, 61- and 62-bit
-chains, aliasing, graph capture, a decryption under real keys, and fhecore.polyeval's Chebyshev
+include/fhecore.h) against pyoracle's lincomb / mul_plain, bit for bit: every output level, mixed
+input levels, 1 .. 16 terms, the constant, the fused rescale, the worst-case accumulation on 60-,
+61- and 62-bit chains, aliasing, graph capture, a decryption under real keys, and fhecore.polyeval's Chebyshev
 evaluation on the GPU backend against the CPU backend's bits."""
 import ctypes
 import random
@@ -9,10 +9,13 @@ import random
 import numpy as np
 import pytest
 
+import cases
 import coracle
-import plain_ref
+import pyoracle
+from refs import c_ntt
 
 pytestmark = pytest.mark.gpu
+CHEB = cases.CHEB
 
 
 @pytest.fixture(scope="module")
@@ -75,7 +78,7 @@ def test_lincomb_every_level(fc, log_n, L, K, dnum, bits):
         sums = {}
         for t in range(16):
             for b in range(3):
-                run[b] = plain_ref.lincomb_level([run[b], pool[t][b]], [1, ks[t]], qs, level)
+                run[b] = pyoracle.lincomb([run[b], pool[t][b]], [1, ks[t]], qs, level=level)
             if t + 1 in COUNTS:
                 sums[t + 1] = [r.copy() for r in run]
         refs = {}
@@ -84,10 +87,10 @@ def test_lincomb_every_level(fc, log_n, L, K, dnum, bits):
             key = (count, const, rescale, b)
             if key not in refs:
                 if rescale:
-                    refs[key] = u64(plain_ref._rescale(want(count, const, False, b), ql))
+                    refs[key] = u64(pyoracle.rescale_ct(want(count, const, False, b), ql, c_ntt()))
                 else:
-                    refs[key] = u64(plain_ref.lincomb_level([sums[count][b]], [1], qs, level,
-                                                            const=k0 if const else None))
+                    refs[key] = u64(pyoracle.lincomb([sums[count][b]], [1], qs, level=level,
+                                                     const=k0 if const else None))
             return refs[key]
 
         for count in COUNTS:
@@ -122,15 +125,15 @@ def test_worst_case_accumulation(fc, bits):
     cts = [fc.to_device(top) for _ in range(16)]
     got = fc.to_host(ctx.lincomb(cts, ctx.encode_scalars([-1] * 17, exact=True), const=True))
     assert (got[:, 0] == 15).all() and (got[:, 1] == 16).all()
-    want = plain_ref.lincomb_level([top[0]] * 16, [-1] * 16, qs, L, const=-1)
+    want = pyoracle.lincomb([top[0]] * 16, [-1] * 16, qs, level=L, const=-1)
     assert (got[0] == u64(want)).all() and (got[1] == u64(want)).all()
-    want_r = plain_ref._rescale(want, qs)
+    want_r = pyoracle.rescale_ct(want, qs, c_ntt())
     got_r = fc.to_host(ctx.lincomb(cts, ctx.encode_scalars([-1] * 17, exact=True), const=True,
                                    rescale=True))
     assert (got_r[0] == u64(want_r)).all() and (got_r[1] == u64(want_r)).all()
     bits01 = [t % 2 for t in range(16)]
     got = fc.to_host(ctx.lincomb(cts, ctx.encode_scalars(bits01 + [0], exact=True), const=True))
-    want = plain_ref.lincomb_level([top[0]] * 16, bits01, qs, L, const=0)
+    want = pyoracle.lincomb([top[0]] * 16, bits01, qs, level=L, const=0)
     assert (got[0] == u64(want)).all() and (got[1] == u64(want)).all()
     for j, q in enumerate(qs):  # eight times q - 1
         assert (got[:, :, j] == (8 * (q - 1)) % q).all()
@@ -179,8 +182,8 @@ def test_mul_plain_every_level(fc, log_n, L, K, dnum, bits):
                     assert (got == want).all(), (level, rows, pt_batch, rescale)
                     if rows == L:  # and the reference itself
                         for b in range(batch):
-                            ref = plain_ref.mul_plain_level(ct[b], pt[b % pt_batch], qs, level,
-                                                            rescale)
+                            ref = pyoracle.mul_plain(ct[b], pt[b % pt_batch], qs, level=level,
+                                                     rescale=rescale, ntt=c_ntt())
                             assert (got[b] == u64(ref)).all(), (level, pt_batch, rescale, b)
     # in place without rescale
     ct = d(rand(qs[:2], log_n, (batch, 2), seed=40))
@@ -303,7 +306,7 @@ def test_graph_replay(fc):
 
 
 def cheb_ctx(fc):
-    return ctx_for(fc, plain_ref.LOG_N, plain_ref.L, plain_ref.K, plain_ref.DNUM, plain_ref.BITS)
+    return ctx_for(fc, CHEB.log_n, CHEB.L, CHEB.nspecial, CHEB.dnum, CHEB.bits)
 
 
 def test_decrypts_correctly_under_real_keys(fc):
@@ -314,7 +317,7 @@ def test_decrypts_correctly_under_real_keys(fc):
     coefficient units at the OUTPUT scale) is 2^-10 of the inputs' own precision.  What remains is
     the encryption error, sigma 3.24 per coefficient (centred binomial, eta = 21) against the
     encoder's rounding sigma 0.29: a ratio of 11.2 sqrt(k_1^2 + k_2^2) = 10.1 plus the input
-    rounding itself -- CPU restatement of this run (pyoracle.encrypt_sk, plain_ref): 9.8x.
+    rounding itself -- CPU restatement of this run (pyoracle.encrypt_sk, pyoracle.lincomb): 9.8x.
     Public-key encryption (error e u + e_0 + e_1 s, ~400x) could not meet the bound."""
     from fhecore.ckks import Encoder, from_rns, to_rns
 
@@ -345,13 +348,13 @@ def test_decrypts_correctly_under_real_keys(fc):
 def _gpu_cheb(fc, degree):
     from fhecore import polyeval
 
-    su = plain_ref.cheb_setup()
+    su = cases.setup(CHEB)
     ctx = cheb_ctx(fc)
     assert ctx.moduli == su["qs"] and ctx.special == su["ps"]
-    key = (fc.to_device(u64(su["evk_b"])), fc.to_device(u64(su["evk_a"])))
+    key = (fc.to_device(u64(su["relin"][0])), fc.to_device(u64(su["relin"][1])))
     be = polyeval.GpuBackend(ctx, key)
-    ct = polyeval.Ct(fc.to_device(u64(su["ct"])), plain_ref.L, plain_ref.DELTA)
-    c = plain_ref.cheb_coeffs(degree)
+    ct = polyeval.Ct(fc.to_device(u64(su["ct"])), CHEB.L, CHEB.delta)
+    c = cases.cheb_coeffs(degree)
     return polyeval.chebyshev_eval(be, ct, c), c
 
 
@@ -359,19 +362,19 @@ def test_chebyshev_eval_matches_the_cpu_backend_bit_for_bit(fc):
     """The degree-7 run of tests/test_plain_cpu.py with the same seeds: both backends receive the
     same integer scalars, so the final ciphertext is the same bits."""
     out, _ = _gpu_cheb(fc, 7)
-    ref, err = plain_ref.cheb_cpu(7)
+    ref, err = cases.run_cpu(CHEB, 7)
     assert (out.level, out.scale) == (ref.level, ref.scale)
     assert (fc.to_host(out.data) == u64(ref.data)).all()
-    assert err < 4 * plain_ref.CHEB_ERR_DEG7
+    assert err < 4 * cases.CHEB_ERR_DEG7
 
 
 def test_chebyshev_eval_degree_15(fc):
     """Degree 15 (m = 4, giants T_4, T_8; five levels) against chebval alone.  The CPU backend
     measured 2.03e-12 for this run, below the degree-7 figure, so the bound stays 4x that one."""
     out, c = _gpu_cheb(fc, 15)
-    assert out.level == plain_ref.L - 5
-    su = plain_ref.cheb_setup()
-    got = plain_ref.cheb_decode(fc.to_host(out.data), out.level, out.scale)
+    assert out.level == CHEB.L - 5
+    su = cases.setup(CHEB)
+    got = cases.decrypt_decode(CHEB, fc.to_host(out.data), out.level, out.scale)
     err = np.abs(got - np.polynomial.chebyshev.chebval(su["x"], c)).max()
     print(f"degree 15: max slot error {err:.3e}")
-    assert err < 4 * plain_ref.CHEB_ERR_DEG7
+    assert err < 4 * cases.CHEB_ERR_DEG7

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import bootstrap_ref as br
+import cases
 import coracle
 import encode_ref
 import sparse_pack_ref as sp
@@ -352,7 +353,7 @@ def test_encode_diagonals_passes_log_slots_through(fc):
 
 @pytest.fixture(scope="module")
 def bctx(fc):
-    su = sp.setup()
+    su = cases.setup(cases.SPARSE)
     c = fc.Context(br.LOG_N, moduli=su["qs"], special=su["ps"], dnum=br.DNUM)
     assert c.moduli == su["qs"] and c.special == su["ps"]
     return c
@@ -369,17 +370,17 @@ def test_sparse_bootstrap_matches_the_cpu_backend_bit_for_bit(fc, bctx):
     from fhecore import bootstrap as bs
     from fhecore.polyeval import Ct
 
-    su = sp.setup()
+    su = cases.setup(cases.SPARSE)
     d = lambda key: (fc.to_device(u64(key[0])), fc.to_device(u64(key[1])))  # noqa: E731
     be = bs.GpuBackend(bctx, relin_key=d(su["relin"]),
                        rot_keys={k: d(v) for k, v in su["rot"].items()})
     boot = bs.Bootstrapper(be, **sp.PARAMS)
     ct = fc.to_device(u64(np.asarray(su["ct"])[:, :1]))
     out = boot.bootstrap(Ct(ct, 1, sp.IN_SCALE))
-    ref, err = sp.bootstrap_cpu()
+    ref, err = cases.run_cpu(cases.SPARSE)
     assert (out.level, out.scale) == (ref.level, ref.scale)
     assert (fc.to_host(out.data) == u64(ref.data)).all()
-    assert err < br.MARGIN * sp.SPARSE_BOOTSTRAP_ERR
+    assert err < cases.MARGIN * cases.SPARSE_BOOTSTRAP_ERR
 
 
 def test_sparse_bootstrap_under_device_keys(fc, bctx):
@@ -390,7 +391,7 @@ def test_sparse_bootstrap_under_device_keys(fc, bctx):
     from fhecore import bootstrap as bs
     from fhecore.polyeval import Ct
 
-    su = sp.setup()
+    su = cases.setup(cases.SPARSE)
     sk = bctx.keygen_secret(seed=61, hamming_weight=br.HAMMING)
     be = bs.GpuBackend(bctx, sk=sk, seed=2000)
     boot = bs.Bootstrapper(be, **sp.PARAMS)
@@ -401,12 +402,12 @@ def test_sparse_bootstrap_under_device_keys(fc, bctx):
     assert tuple(out.data.shape) == (2, br.OUT_LEVEL, 1 << br.LOG_N)
 
     def slots(c):
-        return sp.decode_case(fc.to_host(bctx.decrypt(c.data, sk)), c.level, c.scale)
+        return cases.decode(cases.SPARSE, fc.to_host(bctx.decrypt(c.data, sk)), c.level, c.scale)
 
     err = float(np.abs(slots(out) - su["z"]).max())
     print(f"sparse bootstrap under device keys: max slot error {err:.4e} "
-          f"(CPU run {sp.SPARSE_BOOTSTRAP_ERR:.4e})")
-    assert err < 2 * sp.SPARSE_BOOTSTRAP_ERR
+          f"(CPU run {cases.SPARSE_BOOTSTRAP_ERR:.4e})")
+    assert err < 2 * cases.SPARSE_BOOTSTRAP_ERR
     # the device decoder reads the same slots
     dev = host(bctx.decode(bctx.decrypt(out.data, sk), float(out.scale), level=out.level,
                            log_slots=sp.LOG_SLOTS))
@@ -415,4 +416,4 @@ def test_sparse_bootstrap_under_device_keys(fc, bctx):
     assert again.level == br.OUT_LEVEL
     err2 = float(np.abs(slots(again) - su["z"]).max())
     print(f"second sparse bootstrap: max slot error {err2:.4e}")
-    assert err2 < 4 * sp.SPARSE_BOOTSTRAP_ERR
+    assert err2 < 4 * cases.SPARSE_BOOTSTRAP_ERR

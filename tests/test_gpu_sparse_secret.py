@@ -1,11 +1,10 @@
-"""fhe_keygen_secret_sparse on the GPU (csrc/keygen.hip): the INTT of sk against tests/sparse_ref.py
-bit for bit on every one of the L + K limbs, the refusals, and keygen_secret without the keyword
+"""fhe_keygen_secret_sparse on the GPU (csrc/keygen.hip): the INTT of sk against
+pyoracle.sparse_secret_coefficients bit for bit on every one of the L + K limbs, the refusals, and keygen_secret without the keyword
 unchanged against pyoracle."""
 import numpy as np
 import pytest
 
 import pyoracle
-import sparse_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +32,7 @@ def test_sparse_secret_matches_the_reference_on_every_limb(fc, ctxs, log_n, h, s
     sk = ctx.keygen_secret(seed=seed, hamming_weight=h)
     assert tuple(sk.shape) == (ctx.L + ctx.K, 1 << log_n)
     coef = fc.to_host(ctx.intt(sk))
-    want = sparse_ref.coefficients(seed, h, log_n)
+    want = pyoracle.sparse_secret_coefficients(seed, h, log_n)
     for limb, q in enumerate(ctx.all_moduli):
         assert (coef[limb] == (want % q).astype(np.uint64)).all(), limb
     assert np.count_nonzero(coef[0]) == h
@@ -42,7 +41,7 @@ def test_sparse_secret_matches_the_reference_on_every_limb(fc, ctxs, log_n, h, s
 def test_sparse_secret_ntt_form_matches_the_reference(fc, ctxs):
     ctx = ctxs[10]
     sk = fc.to_host(ctx.keygen_secret(seed=9, hamming_weight=28)).astype(object)
-    assert (sk == sparse_ref.keygen_secret_sparse(9, 28, ctx.all_moduli, 10)).all()
+    assert (sk == pyoracle.keygen_secret_sparse(9, 28, ctx.all_moduli, 10)).all()
 
 
 def test_bad_weights_are_refused(fc, ctxs):

@@ -1,5 +1,5 @@
 """ModRaise without a GPU: the C entry points exist and refuse a null context, the reference
-(tests/modraise_ref.py) is checked against its own definition through the CRT, and the identity a
+(pyoracle.mod_raise) is checked against its own definition through the CRT, and the identity a
 bootstrap relies on -- the raised ciphertext decrypts to m + q_0 I with a small integer polynomial
 I -- holds on the reference under a real key."""
 import random
@@ -7,11 +7,12 @@ import random
 import numpy as np
 
 import coracle
-import modraise_ref
 import pyoracle
+import refs
 
 LOG_N = 10
 N = 1 << LOG_N
+NTT = refs.c_ntt()
 
 
 def chains():
@@ -55,13 +56,13 @@ def test_reference_against_its_definition():
                           axis=1)  # (2, in_level, N)
             for out_level in (1, 2, len(qs)):
                 ql = qs[:out_level]
-                out = modraise_ref.mod_raise(ct, qs, in_level, out_level)
+                out = pyoracle.mod_raise(ct, qs, in_level, out_level, ntt=NTT)
                 assert out.shape == (2, out_level, N)
                 assert (out[:, 0] == ct[:, 0].astype(object)).all()
                 assert all((out[:, l] < ql[l]).all() and (out[:, l] >= 0).all()
                            for l in range(out_level))
                 # across its limbs the result is one integer polynomial: the centred lift
-                c = modraise_ref.centred_lift(ct, qs)
+                c = pyoracle.centred_lift(ct, qs, NTT)
                 assert (abs(c) <= (q0 - 1) // 2).all()
                 coef = coracle.ntt_inv(out.astype(np.uint64), ql)
                 for h in range(2):
@@ -78,10 +79,10 @@ def test_boundary_coefficients():
         vals = [0, 1, h, h + 1, q0 - 1]
         x = np.array([vals[i % 5] for i in range(N)], dtype=np.uint64)
         ct = coracle.ntt_fwd(np.stack([x, x[::-1].copy()])[:, None, :], [q0])
-        c = modraise_ref.centred_lift(ct, qs)
+        c = pyoracle.centred_lift(ct, qs, NTT)
         want = {0: 0, 1: 1, h: h, h + 1: -h, q0 - 1: -1}
         assert all(c[0, i] == want[vals[i % 5]] for i in range(N))
-        out = modraise_ref.mod_raise(ct, qs, 1, len(qs))
+        out = pyoracle.mod_raise(ct, qs, 1, len(qs), ntt=NTT)
         coef = coracle.ntt_inv(out.astype(np.uint64), qs)
         for l, q in enumerate(qs):
             assert all(int(coef[0, l, i]) == want[vals[i % 5]] % q for i in range(N))
@@ -107,7 +108,7 @@ def test_raised_ciphertext_decrypts_to_m_plus_q0_I():
         m1 = coracle.ntt_inv(np.asarray(d1, dtype=np.uint64), qs[:1])[0].astype(object)
         m1 = np.where(m1 > (q0 - 1) // 2, m1 - q0, m1)
         assert max(abs(a - b) for a, b in zip(m1, m)) <= 21  # the encryption error (eta = 21)
-        up = modraise_ref.mod_raise(low, qs, 1, L)
+        up = pyoracle.mod_raise(low, qs, 1, L, ntt=NTT)
         dec = pyoracle.decrypt(up, sk_ntt, qs)
         y = pyoracle.crt_centered(coracle.ntt_inv(np.asarray(dec, dtype=np.uint64), qs), qs)
         assert ((y - m1) % q0 == 0).all()

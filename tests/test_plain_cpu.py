@@ -1,5 +1,5 @@
 """Level-aware plaintext arithmetic and the Chebyshev evaluator without a GPU: the new C entry
-points exist and refuse a null context, the reference restatement (tests/plain_ref.py) is pinned
+points exist and refuse a null context, the reference (pyoracle.lincomb / mul_plain) is pinned
 against a direct CRT computation over Z[X]/(X^N + 1), and fhecore.polyeval.chebyshev_eval on the
 CPU backend decrypts to the series it was given."""
 import math
@@ -9,9 +9,12 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import cases
 import coracle
-import plain_ref
 import pyoracle
+import refs
+
+CHEB = cases.CHEB
 
 
 def test_surface():
@@ -50,8 +53,8 @@ def _negacyclic(a, b):
 
 def test_plain_ref_against_direct_crt():
     """k_1 a + k_2 b + k_0 over Z[X]/(X^N + 1) for small-coefficient polynomials lifted to the
-    integers, reduced mod each prime, equals lincomb_level on their NTT forms; after rescale both
-    equal floor((X + q/2) / q) of the CRT value X in [0, Q).  mul_plain_level is the negacyclic
+    integers, reduced mod each prime, equals pyoracle.lincomb on their NTT forms; after rescale both
+    equal floor((X + q/2) / q) of the CRT value X in [0, Q).  mul_plain is the negacyclic
     product.  A 'ciphertext' here is any pair of polynomials: the constant goes to the first."""
     log_n, nl = 10, 3
     n = 1 << log_n
@@ -69,23 +72,24 @@ def test_plain_ref_against_direct_crt():
     direct[0][0] += k0  # the constant polynomial k_0
     for level in (3, 2):
         ql = qs[:level]
-        got = plain_ref.lincomb_level([a, b], [k1, k2], qs, level, const=k0)
+        got = pyoracle.lincomb([a, b], [k1, k2], qs, level=level, const=k0)
         assert got.shape == (2, level, n)
         for h in range(2):
             assert (got[h] == ntt(direct[h], ql).astype(object)).all(), (level, h)
-        res = plain_ref.lincomb_level([a, b], [k1, k2], qs, level, const=k0, rescale=True)
+        res = pyoracle.lincomb([a, b], [k1, k2], qs, level=level, const=k0, rescale=True,
+                               ntt=refs.c_ntt())
         Ql = math.prod(ql)
         for h in range(2):
             want = [((v % Ql) + ql[-1] // 2) // ql[-1] for v in direct[h]]
             assert (res[h] == ntt(want, ql[:-1]).astype(object)).all(), (level, h, "rescaled")
     # a scalar of zero drops its term; one term with scalar 1 is the slice
-    assert (plain_ref.lincomb_level([a, b], [1, 0], qs, 2) == a[:, :2].astype(object)).all()
+    assert (pyoracle.lincomb([a, b], [1, 0], qs, level=2) == a[:, :2].astype(object)).all()
     pt = ntt(polys[1][0], qs)
     prods = [_negacyclic(polys[0][h], polys[1][0]) for h in range(2)]
-    got = plain_ref.mul_plain_level(a[:, :2], pt, qs, 2)
+    got = pyoracle.mul_plain(a[:, :2], pt, qs, level=2)
     for h in range(2):
         assert (got[h] == ntt(prods[h], qs[:2]).astype(object)).all()
-    res = plain_ref.mul_plain_level(a, pt, qs, 3, rescale=True)
+    res = pyoracle.mul_plain(a, pt, qs, level=3, rescale=True, ntt=refs.c_ntt())
     for h in range(2):
         want = [((v % Q) + qs[-1] // 2) // qs[-1] for v in prods[h]]
         assert (res[h] == ntt(want, qs[:2]).astype(object)).all()
@@ -99,25 +103,24 @@ def test_chebyshev_eval_cpu_backend():
     rounding differences between numpy builds only."""
     from fhecore import polyeval
 
-    out, err = plain_ref.cheb_cpu(7)
+    out, err = cases.run_cpu(CHEB, 7)
     print(f"degree 7: level {out.level}, max slot error {err:.3e}")
-    assert out.level == plain_ref.L - polyeval.levels_needed(7) == 4
-    assert out.scale == Fraction(plain_ref.DELTA)
-    assert err < 4 * plain_ref.CHEB_ERR_DEG7
+    assert out.level == CHEB.L - polyeval.levels_needed(7) == 4
+    assert out.scale == Fraction(CHEB.delta)
+    assert err < 4 * cases.CHEB_ERR_DEG7
 
 
 def test_chebyshev_eval_errors():
     from fhecore import polyeval
 
-    su = plain_ref.cheb_setup()
-    be = plain_ref.CpuBackend(su["qs"], su["ps"], plain_ref.DNUM, su["evk_b"], su["evk_a"])
-    c = plain_ref.cheb_coeffs(7)
+    su, be = cases.setup(CHEB), cases.backend(CHEB)
+    c = cases.cheb_coeffs(7)
     # degree 7 consumes 4 levels and must leave one: level 4 is too low (nothing is computed)
     with pytest.raises(ValueError, match="too few levels"):
-        polyeval.chebyshev_eval(be, polyeval.Ct(su["ct"][:, :4], 4, plain_ref.DELTA), c)
+        polyeval.chebyshev_eval(be, polyeval.Ct(su["ct"][:, :4], 4, CHEB.delta), c)
     with pytest.raises(ValueError, match="degree"):
-        polyeval.chebyshev_eval(be, polyeval.Ct(su["ct"], plain_ref.L, plain_ref.DELTA), [1.0] * 65)
+        polyeval.chebyshev_eval(be, polyeval.Ct(su["ct"], CHEB.L, CHEB.delta), [1.0] * 65)
     # a scale far from the primes: T_3 = 2 T_2 T_1 - T_1 meets scales 1.37^3 and 1.37 times 2^50
     with pytest.raises(ValueError, match="not an integer"):
-        polyeval.chebyshev_eval(be, polyeval.Ct(su["ct"], plain_ref.L, 1.37 * plain_ref.DELTA), c)
+        polyeval.chebyshev_eval(be, polyeval.Ct(su["ct"], CHEB.L, 1.37 * CHEB.delta), c)
     assert [polyeval.levels_needed(d) for d in (1, 3, 7, 15, 31, 63)] == [1, 2, 4, 5, 6, 7]

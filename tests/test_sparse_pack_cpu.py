@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import bootstrap_ref as br
+import cases
 import encode_ref
 import sparse_pack_ref as sp
 
@@ -177,14 +178,14 @@ def test_sparse_bootstrap_decrypts_to_the_input_slots():
     expected at the same message ratio, and far from the 2 x 2.833e-05 that would mean a wrong
     constant in the composition.  Nearly all of it is EvalMod's cubic term of these 64 slots,
     which the exact sine on the bare coefficients gives as 2.47e-05."""
-    out, err = sp.bootstrap_cpu()
+    out, err = cases.run_cpu(cases.SPARSE)
     print(f"sparse bootstrap: level {out.level}, scale / input scale "
           f"{float(out.scale) / sp.IN_SCALE:.12f}, max slot error {err:.4e}")
-    assert sp.SPARSE_BOOTSTRAP_ERR <= br.BOOTSTRAP_ERR
-    assert err < br.MARGIN * sp.SPARSE_BOOTSTRAP_ERR
+    assert cases.SPARSE_BOOTSTRAP_ERR <= cases.BOOTSTRAP_ERR
+    assert err < cases.MARGIN * cases.SPARSE_BOOTSTRAP_ERR
     assert out.level == br.OUT_LEVEL and np.asarray(out.data).shape == (2, br.OUT_LEVEL, N)
     assert abs(float(out.scale) / sp.IN_SCALE - 1) < 2.0 ** -26
-    su = sp.setup()
+    su = cases.setup(cases.SPARSE)
     cubic = sp.cubic_term(su["z"], sp.IN_SCALE, su["qs"][0], sp.LOG_SLOTS)
     print(f"cubic term alone: {cubic:.4e}")
     assert abs(err - cubic) < 0.05 * cubic
@@ -195,7 +196,7 @@ def test_the_cubic_term_follows_the_message_ratio_not_the_packing():
     plaintext of n_s slots has coefficients sqrt(gap) larger, and the exact sine on the bare
     coefficients -- no ciphertext, no bootstrap -- leaves about gap times the slot error.  At the
     same coefficient size the term is full packing's."""
-    su, full = sp.setup(), br.setup()
+    su, full = cases.setup(cases.SPARSE), cases.setup(cases.BOOTSTRAP)
     q0 = su["qs"][0]
     at_delta = sp.cubic_term(su["z"], br.DELTA, q0, sp.LOG_SLOTS)
     at_ratio = sp.cubic_term(su["z"], sp.IN_SCALE, q0, sp.LOG_SLOTS)
@@ -216,31 +217,32 @@ def test_the_cubic_term_follows_the_message_ratio_not_the_packing():
 def test_sparse_bootstrapper_constants_and_refusals():
     from fhecore import bootstrap as bs
 
-    boot = bs.Bootstrapper(sp.backend(), **sp.PARAMS)
-    full = bs.Bootstrapper(br.backend(), **br.PARAMS)
+    boot = bs.Bootstrapper(cases.backend(cases.SPARSE), **sp.PARAMS)
+    full = bs.Bootstrapper(cases.backend(cases.BOOTSTRAP), **br.PARAMS)
     assert boot.subsum_steps == [64, 128, 256] and full.subsum_steps == []
     # 2 n_s gap = N: the constants and scales are full packing's, to the digit
     assert boot.scale_cts == full.scale_cts and boot.mult_stc == full.mult_stc
     assert boot.out_level == br.OUT_LEVEL
-    be = sp.backend()
+    be = cases.backend(cases.SPARSE)
     for bad in (2, -1, LOG_N):
         with pytest.raises(ValueError, match="log_slots"):
             bs.Bootstrapper(be, **dict(sp.PARAMS, log_slots=bad))
     with pytest.raises(ValueError, match="more groups"):
-        bs.Bootstrapper(br.backend(), **dict(br.PARAMS, cts_groups=1, log_slots=LOG_N - 1))
+        bs.Bootstrapper(cases.backend(cases.BOOTSTRAP),
+                        **dict(br.PARAMS, cts_groups=1, log_slots=LOG_N - 1))
     assert bs.BootstrapParams().log_slots is None
 
 
 def test_full_packing_bootstrap_is_unchanged():
-    """log_slots = log_n - 1 is the full-packing path: the bits of bootstrap_ref.bootstrap_cpu(),
+    """log_slots = log_n - 1 is the full-packing path: the bits of the BOOTSTRAP case's CPU run,
     which runs Bootstrapper with the default None."""
     from fhecore import bootstrap as bs
     from fhecore.polyeval import Ct
 
-    ref, err = br.bootstrap_cpu()
-    assert err < br.MARGIN * br.BOOTSTRAP_ERR
-    su = br.setup()
-    boot = bs.Bootstrapper(br.backend(), **dict(br.PARAMS, log_slots=LOG_N - 1))
+    ref, err = cases.run_cpu(cases.BOOTSTRAP)
+    assert err < cases.MARGIN * cases.BOOTSTRAP_ERR
+    su = cases.setup(cases.BOOTSTRAP)
+    boot = bs.Bootstrapper(cases.backend(cases.BOOTSTRAP), **dict(br.PARAMS, log_slots=LOG_N - 1))
     out = boot.bootstrap(Ct(np.asarray(su["ct"])[:, :1], 1, br.DELTA))
     assert (out.level, out.scale) == (ref.level, ref.scale)
     assert (np.asarray(out.data) == np.asarray(ref.data)).all()
