@@ -956,6 +956,56 @@ int fhe_decode_sparse(const fhe_ctx* c, double* slots, const uint64_t* pt, doubl
                      ws, s);
 }
 
+int fhe_decrypt_slots(const fhe_ctx* c, double* slots, const uint64_t* ct, const uint64_t* sk,
+                      double delta, uint32_t log_slots, uint32_t level, uint32_t batch, void* ws,
+                      fhe_stream_t s) {
+  const std::string w("fhe_decrypt_slots");
+  if (!c) {
+    set_error(w + ": null context");
+    return kInvalid;
+  }
+  if (!slots || !ct || !sk) {
+    set_error(w + ": null data pointer");
+    return kInvalid;
+  }
+  if (level == 0 || level > c->L) {
+    set_error(w + ": level must be in [1, L]");
+    return kInvalid;
+  }
+  if (log_slots > c->log_n - 1) {
+    set_error(w + ": log_slots must be in [0, log_n - 1]");
+    return kInvalid;
+  }
+  if (!(std::isfinite(delta) && delta > 0)) {
+    set_error(w + ": delta must be finite and positive");
+    return kInvalid;
+  }
+  const uint64_t n = c->n;
+  const uint64_t* sw = reinterpret_cast<const uint64_t*>(slots);
+  const uint64_t slot_words = (uint64_t)batch << (log_slots + 1);
+  if (spans_overlap(sw, slot_words, ct, (uint64_t)batch * 2 * level * n)) {
+    set_error(w + ": slots overlaps ct");
+    return kInvalid;
+  }
+  if (spans_overlap(sw, slot_words, sk, std::min<uint64_t>(level, 2) * n)) {
+    set_error(w + ": slots overlaps sk");
+    return kInvalid;
+  }
+  const size_t ws_bytes = decode_workspace_bytes(c, batch);
+  if (ws && spans_overlap(sw, slot_words, static_cast<const uint64_t*>(ws), ws_bytes / 8)) {
+    set_error(w + ": slots overlaps the workspace");
+    return kInvalid;
+  }
+  if (batch == 0) return kOk;
+  int rc = ensure_ws(c, ws_bytes, &ws, hs(s));
+  if (rc) return rc;
+  // FHECORE_DECRYPT_UNFUSED=1: the form of wide contexts (the product written out, then the whole
+  // inverse transform) on any context (the same bits; tools/decrypt_times.py times the two)
+  const char* u = std::getenv("FHECORE_DECRYPT_UNFUSED");
+  return launch_decrypt_slots(c, slots, ct, sk, delta, log_slots, level, batch, ws,
+                              u && u[0] == '1', hs(s));
+}
+
 size_t fhe_encrypt_workspace(const fhe_ctx* c, uint32_t level, uint32_t batch) {
   return c && level >= 1 && level <= c->L ? encrypt_workspace_bytes(c, level, batch) : 0;
 }

@@ -508,17 +508,15 @@ int launch_encode(const fhe_ctx* c, u64* out, const double* slots, double delta,
   return kOk;
 }
 
-int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 log_slots,
-                  u32 pt_rows, u32 level, u32 count, void* ws, hipStream_t s) {
-  if (count == 0) return kOk;
+namespace {
+// What fhe_decode and fhe_decrypt_slots share: x = ws [count][nl][N] holds the inverse transforms
+// of limb 0 (and 1); centring into the doubles behind it, then the special FFT into slots.
+int decode_tail(const fhe_ctx* c, double* slots, double delta, u32 log_slots, u32 nl, u32 count,
+                void* ws, hipStream_t s) {
   const u64 n = c->n;
-  const u32 nl = level >= 2 ? 2 : 1;
-  u64* x = static_cast<u64*>(ws);  // [count][nl][N]
+  u64* x = static_cast<u64*>(ws);
   double* d = reinterpret_cast<double*>(x + (u64)2 * count * n);
   int rc;
-  if ((rc = launch_ntt_strided(c, false, pt, (u64)pt_rows * n, x, (u64)nl * n, count, 0, nl, s)))
-    return rc;
-  prof_mark(s, "decode_intt");
   const bool full = log_slots == c->log_n - 1;
   if (full) {
     if ((rc = check_grid(n / kFftThreads, kFftThreads, count, 1, "decode"))) return rc;
@@ -540,6 +538,43 @@ int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, 
     return rc;
   prof_mark(s, "decode_fft");
   return kOk;
+}
+}  // namespace
+
+int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 log_slots,
+                  u32 pt_rows, u32 level, u32 count, void* ws, hipStream_t s) {
+  if (count == 0) return kOk;
+  const u64 n = c->n;
+  const u32 nl = level >= 2 ? 2 : 1;
+  u64* x = static_cast<u64*>(ws);  // [count][nl][N]
+  if (int rc = launch_ntt_strided(c, false, pt, (u64)pt_rows * n, x, (u64)nl * n, count, 0, nl, s))
+    return rc;
+  prof_mark(s, "decode_intt");
+  return decode_tail(c, slots, delta, log_slots, nl, count, ws, s);
+}
+
+int launch_decrypt_slots(const fhe_ctx* c, double* slots, const u64* ct, const u64* sk,
+                         double delta, u32 log_slots, u32 level, u32 batch, void* ws, bool unfused,
+                         hipStream_t s) {
+  if (batch == 0) return kOk;
+  const u64 n = c->n;
+  const u32 nl = level >= 2 ? 2 : 1;
+  u64* x = static_cast<u64*>(ws);  // [batch][nl][N]: c0 + c1 s, inverse-transformed in place
+  int rc;
+  if (!c->wide && !unfused) {
+    // the product rides on the inverse transform's first pass (ntt.hip k_dec_row)
+    if ((rc = launch_dec_row(c, ct, sk, x, level, nl, batch, s))) return rc;
+    prof_mark(s, "decrypt_row");
+    if ((rc = launch_ntt_col_inv(c, x, (u64)nl * n, x, (u64)nl * n, batch, 0, nl, s, nullptr,
+                                 false, "decode_col_inv")))
+      return rc;
+  } else {
+    if ((rc = launch_decrypt_rows(c, x, ct, sk, level, nl, batch, s))) return rc;
+    prof_mark(s, "decrypt_mac");
+    if ((rc = launch_ntt(c, false, x, x, batch, (u64)nl * n, 0, nl, s))) return rc;
+    prof_mark(s, "decode_intt");
+  }
+  return decode_tail(c, slots, delta, log_slots, nl, batch, ws, s);
 }
 
 }  // namespace fhe

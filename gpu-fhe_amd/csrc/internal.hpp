@@ -161,10 +161,16 @@ int launch_ntt_strided(const fhe_ctx* c, bool forward, const u64* src, u64 spstr
                        const ulonglong2* nfold = nullptr, bool split = false);
 // The second (column) pass of an inverse NTT alone, src [polys][nlimbs][N] (stride spstride,
 // already row-inverted, e.g. by k_ks_row_inner PINV) -> dst (stride dpstride); nfold / split as
-// launch_ntt_strided.
+// launch_ntt_strided; mark: the pass's prof_mark name.
 int launch_ntt_col_inv(const fhe_ctx* c, const u64* src, u64 spstride, u64* dst, u64 dpstride,
                        u32 polys, u32 limb0, u32 nlimbs, hipStream_t s,
-                       const ulonglong2* nfold = nullptr, bool split = false);
+                       const ulonglong2* nfold = nullptr, bool split = false,
+                       const char* mark = "ntt_col_inv");
+// fhe_decrypt_slots' first pass (k_dec_row): the inverse row pass of c0 + c1 s over the limbs
+// l < nl of ct [batch][2][level][N], read through the ciphertext's own strides, into
+// x [batch][nl][N]; launch_ntt_col_inv on x finishes the transform.  Narrow contexts only.
+int launch_dec_row(const fhe_ctx* c, const u64* ct, const u64* sk, u64* x, u32 level, u32 nl,
+                   u32 batch, hipStream_t s);
 // Column-forward pass only (first half of a forward NTT; the key-switch's fused row kernel
 // finishes it).
 int launch_ntt_col_fwd(const fhe_ctx* c, const u64* src, u64 spstride, u64* dst, u64 dpstride,
@@ -525,6 +531,16 @@ int launch_encode_spread(const fhe_ctx* c, u64* out, const long long* cf, u32 ro
 // [count][2^log_slots][2]; below full packing only the coefficients at the multiples of gap are read
 int launch_decode(const fhe_ctx* c, double* slots, const u64* pt, double delta, u32 log_slots,
                   u32 pt_rows, u32 level, u32 count, void* ws, hipStream_t s);
+// fhe_decrypt_slots: launch_decode of c0 + c1 s without the [level][N] plaintext.  ct
+// [batch][2][level][N], sk [L + K][N] (rows l < min(level, 2) read).  The fused form (narrow
+// contexts) folds the product into the inverse transform's first pass (launch_dec_row); unfused,
+// and on wide contexts, mac_s writes the limbs read and the ordinary inverse runs in place.
+int launch_decrypt_slots(const fhe_ctx* c, double* slots, const u64* ct, const u64* sk,
+                         double delta, u32 log_slots, u32 level, u32 batch, void* ws, bool unfused,
+                         hipStream_t s);
+// (keygen.hip) x [batch][nl][N] = c0 + c1 s over the limbs l < nl of ct [batch][2][level][N]
+int launch_decrypt_rows(const fhe_ctx* c, u64* x, const u64* ct, const u64* sk, u32 level, u32 nl,
+                        u32 batch, hipStream_t s);
 size_t decode_workspace_bytes(const fhe_ctx* c, u32 count);
 
 // ---- launchers (keygen.hip): batched encryption at any level ------------------------------

@@ -280,6 +280,14 @@ __global__ __launch_bounds__(kThreads) void k_sparse_spread(u64* __restrict__ sk
 
 }  // namespace
 
+// fhe_decrypt's product on the limbs l < nl only, into x [batch][nl][N] (fhe_decrypt_slots'
+// unfused form: the decoder reads no other limb)
+int launch_decrypt_rows(const fhe_ctx* c, u64* x, const u64* ct, const u64* sk, u32 level, u32 nl,
+                        u32 batch, hipStream_t s) {
+  const u64 ln = (u64)level * c->n;
+  return mac_s(c, x, (u64)nl * c->n, ct, 2 * ln, ct + ln, 2 * ln, sk, batch, 0, nl, false, s);
+}
+
 // The workspace of one pass of b ciphertexts, in words (a null base measures):
 //   draws  [3 b N]          u [b][N] then (e0, e1) [b][2][N]; the secret-key form uses e [b][N].
 //                           The encoder's FFT workspace [b][N/2] complex lives here first

@@ -585,6 +585,11 @@ template <int STRIDE, bool NT = false, bool NTS = NT>
 struct GView {
   u64* base;
   u32 lane;
+  // one load with the view's (non-)temporal choice
+  template <class P>
+  __device__ __forceinline__ auto ld(P p) const {
+    return gld<NT>(p);
+  }
   template <class Lay>
   __device__ __forceinline__ void load(u64 (&x)[Lay::E], u32 tp) const {
     const u32 off = lane + tp * STRIDE;
@@ -909,15 +914,53 @@ __global__ __launch_bounds__(kColThreads) __attribute__((amdgpu_waves_per_eu(4, 
                                            pl % nlimbs, tile, tw_all, nfold, mods);
 }
 
+// The inverse row pass's first load (row_tile's load policy): the row's words in linear order,
+// thread t of the row's TPS threads taking the 16-byte pairs t + TPS jj (GView::load_lin).
+// `loc` is the tile's offset inside its polynomial's [nlimbs][N] block (limb and first row).
+struct RowLoadLin {
+  template <u32 TPS, class GIn>
+  __device__ __forceinline__ void load(const GIn& gin, u64, u32, const ModParams*, u64 (&x)[kE],
+                                       u32 t) const {
+    gin.template load_lin<TPS>(x, t);
+  }
+};
+
+// The same load of a ciphertext's c0 + c1 s (k_dec_row): gin views c0, c1 lies `comp` words
+// behind it, and s [..][N] is indexed by `loc` alone (one key for the whole batch).  Each value
+// is k_mac_s's, csub(c0 + mulmod_barrett(c1, s, m), q).  The products are formed pair by pair, so
+// at most one pair of each operand is live next to the 16 results.
+struct RowLoadDec {
+  u64 comp;
+  const u64* sk;
+  template <u32 TPS, class GIn>
+  __device__ __forceinline__ void load(const GIn& gin, u64 loc, u32 limb,
+                                       const ModParams* __restrict__ mods, u64 (&x)[kE],
+                                       u32 t) const {
+    const ModParams m = mods[limb];
+    const gptr_u128 v0 = (gptr_u128)(gin.base + gin.lane) + t;
+    const gptr_u128 v1 = (gptr_u128)(gin.base + comp + gin.lane) + t;
+    const gptr_u128 vs = (gptr_u128)(const_cast<u64*>(sk) + loc + gin.lane) + t;
+#pragma unroll
+    for (int jj = 0; jj < kE / 2; ++jj) {
+      // c0 and c1 are read once, with the view's own (non-)temporal choice; s is re-read by
+      // every ciphertext of the batch and stays cached
+      const u64x2_t a = gin.ld(v0 + jj * TPS), b = gin.ld(v1 + jj * TPS);
+      const u64x2_t w = *(vs + jj * TPS);
+      x[2 * jj] = csub(a.x + mulmod_barrett(b.x, w.x, m), m.q);
+      x[2 * jj + 1] = csub(a.y + mulmod_barrett(b.y, w.y, m), m.q);
+    }
+  }
+};
+
 // One row tile (poly p, limb l, tile) of a row pass (the body of k_ntt_row; lds: G::LDS_R words).
 // The forward stores its last round in linear order through the LDS (XOUT); the inverse loads its
-// first round that way.
-template <int LOGN, bool FWD, int H, bool NTL, bool NTS, int R0 = 1>
+// first round that way, through the load policy `ld` (RowLoadLin: the row as it is).
+template <int LOGN, bool FWD, int H, bool NTL, bool NTS, int R0 = 1, class Ld = RowLoadLin>
 __device__ __forceinline__ void row_tile(u64* lds, const u64* __restrict__ src,
                                          u64* __restrict__ dst, u32 limb0, const PolyMap& pm,
                                          u32 p, u32 l, u32 tile,
                                          const ulonglong2* __restrict__ tw_all,
-                                         const ModParams* __restrict__ mods) {
+                                         const ModParams* __restrict__ mods, const Ld& ld = {}) {
   using G = Geo<LOGN>;
   constexpr u64 N = 1ull << LOGN;
   static_assert(64 % G::TPS_R == 0, "a row must not straddle wavefronts");
@@ -934,7 +977,7 @@ __device__ __forceinline__ void row_tile(u64* lds, const u64* __restrict__ src,
     // redistribute through the LDS (the mirror of pass_run's XOUT store)
     using Rd = Rounds<G::N2>;
     using Lay0 = Layout<G::N2, Rd::kb_inv(0), Rd::lo_inv(0)>;
-    gin.template load_lin<G::TPS_R>(x, t);
+    ld.template load<G::TPS_R>(gin, loc, limb, mods, x, t);
 #pragma unroll
     for (int jj = 0; jj < kE / 2; ++jj) {
       const u32 q = 2 * t + 2 * G::TPS_R * jj;
@@ -2401,6 +2444,40 @@ int lift_col_dispatch(const fhe_ctx* c, const u64* src, u64* dst, u32 polys, con
                                                          c->d_mods);
   return kOk;
 }
+
+// fhe_decrypt_slots' first pass: the inverse row pass (k_ntt_row<.., FWD = false>) of c0 + c1 s,
+// formed by the load (RowLoadDec) instead of read.  ct [batch][2][level][N], of which the limbs
+// l < nl are read through the ciphertext's own strides; x [batch][nl][N] takes what the plain
+// inverse row pass of fhe_decrypt's plaintext would have written.  Items (l, ciphertext, tile) as
+// k_ntt_row's: the limb follows the XCD, so s's row and the row twiddles stay in that XCD's L2.
+template <int LOGN, int H>
+__global__ FHE_KATTR void k_dec_row(const u64* __restrict__ ct, const u64* __restrict__ sk,
+                                    u64* __restrict__ x, u32 level, u32 nl, u32 items,
+                                    const ulonglong2* __restrict__ tw_all,
+                                    const ModParams* __restrict__ mods) {
+  using G = Geo<LOGN>;
+  constexpr u64 N = 1ull << LOGN;
+  __shared__ u64 lds[G::LDS_R];
+  const u32 it = blockIdx.x;
+  if (it >= items) return;
+  u32 l, rest;
+  xcd_limb_split(it, nl, items / nl, l, rest);
+  const PolyMap pm{1, 2 * (u64)level * N, 0, (u64)nl * N, 0, 0};
+  row_tile<LOGN, false, H, false, false, 1>(lds, ct, x, 0u, pm, rest / G::TILES_R, l,
+                                            rest % G::TILES_R, tw_all, mods,
+                                            RowLoadDec{(u64)level * N, sk});
+}
+
+template <int LOGN, int HD>
+int dec_row_dispatch(const fhe_ctx* c, const u64* ct, const u64* sk, u64* x, u32 level, u32 nl,
+                     u32 batch, hipStream_t s) {
+  using G = Geo<LOGN>;
+  const u64 ir = (u64)batch * nl * G::TILES_R;
+  if (int rc = check_grid(item_blocks(ir), G::THR_R, 1, 1, "decrypt_slots")) return rc;
+  k_dec_row<LOGN, inv_h(HD)><<<item_grid(ir), G::THR_R, 0, s>>>(ct, sk, x, level, nl, (u32)ir,
+                                                                c->d_tw_inv, c->d_mods);
+  return kOk;
+}
 #endif  // !FHE_NTT_KS_ONLY
 
 }  // namespace
@@ -2684,7 +2761,7 @@ namespace {
 template <int LOGN, int HD>
 int col_inv_dispatch(const fhe_ctx* c, const u64* src, u64 spstride, u64* dst, u64 dpstride,
                      u32 polys, u32 limb0, u32 nlimbs, hipStream_t s, const ulonglong2* nfold,
-                     bool split) {
+                     bool split, const char* mark) {
   using G = Geo<LOGN>;
   const u64 ic = (u64)polys * nlimbs * G::TILES_C;
   if (int rc = check_grid(item_blocks(ic), G::THR_C, 1, 1, "ntt_col_inv")) return rc;
@@ -2695,7 +2772,7 @@ int col_inv_dispatch(const fhe_ctx* c, const u64* src, u64 spstride, u64* dst, u
       k_ntt_col<LOGN, false, inv_h(HD), false, false, kFinalInvS30>
           <<<item_grid(ic), G::THR_C, 0, s>>>(src, nullptr, dst, nlimbs, limb0, pm, (u32)ic,
                                               c->d_tw_inv, nf, c->d_mods);
-      prof_mark(s, "ntt_col_inv");
+      prof_mark(s, mark);
       return kOk;
     }
   } else if (split) {
@@ -2704,18 +2781,30 @@ int col_inv_dispatch(const fhe_ctx* c, const u64* src, u64 spstride, u64* dst, u
   }
   k_ntt_col<LOGN, false, inv_h(HD)><<<item_grid(ic), G::THR_C, 0, s>>>(
       src, nullptr, dst, nlimbs, limb0, pm, (u32)ic, c->d_tw_inv, nf, c->d_mods);
-  prof_mark(s, "ntt_col_inv");
+  prof_mark(s, mark);
   return kOk;
 }
 }  // namespace
 
 int launch_ntt_col_inv(const fhe_ctx* c, const u64* src, u64 spstride, u64* dst, u64 dpstride,
                        u32 polys, u32 limb0, u32 nlimbs, hipStream_t s, const ulonglong2* nfold,
-                       bool split) {
+                       bool split, const char* mark) {
   if ((u64)polys * nlimbs == 0) return kOk;
   return with_geometry<true>(c, [&](auto n, auto hd) {
     return col_inv_dispatch<n, hd>(c, src, spstride, dst, dpstride, polys, limb0, nlimbs, s, nfold,
-                                   split);
+                                   split, mark);
+  });
+}
+
+int launch_dec_row(const fhe_ctx* c, const u64* ct, const u64* sk, u64* x, u32 level, u32 nl,
+                   u32 batch, hipStream_t s) {
+  if ((u64)batch * nl == 0) return kOk;
+  if (c->wide) {
+    set_error("decrypt_slots: the fused first pass needs every modulus < 2^61");
+    return kUnsupported;
+  }
+  return with_geometry<false>(c, [&](auto n, auto hd) {
+    return dec_row_dispatch<n, hd>(c, ct, sk, x, level, nl, batch, s);
   });
 }
 

@@ -116,6 +116,7 @@ SIGNATURES = {
                                  _vp]),
     "fhe_decode_sparse": (_i32, [_vp, _vp, _vp, ctypes.c_double, _u32, _u32, _u32, _u32, _vp,
                                  _vp]),
+    "fhe_decrypt_slots": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_double, _u32, _u32, _u32, _vp, _vp]),
     "fhe_graph_begin": (_i32, [_vp]),
     "fhe_graph_end": (_i32, [_vp, ctypes.POINTER(_vp)]),
     "fhe_graph_launch": (_i32, [_vp, _vp]),

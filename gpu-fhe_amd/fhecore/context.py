@@ -998,6 +998,41 @@ class Context:
                       "fhe_decode_sparse")
         return out
 
+    def decrypt_slots(self, ct, sk, delta, *, log_slots=None, workspace=None, out=None):
+        """ct [..., 2, level, N] NTT form (the level taken from the shape) -> complex128 slots
+        [..., 2^log_slots] (default: N/2, full packing) in one call (fhe_decrypt_slots): bit for
+        bit decode(decrypt(ct, sk), delta, level=level, log_slots=log_slots), without forming the
+        plaintext: only limb 0 of the ciphertext is read, and limb 1 at level >= 2, and c0 + c1 s
+        is computed by the inverse transform's first pass as it loads.  sk is [L + K, N].
+        workspace: fhe_decode_workspace(ctx, count) bytes; None takes the context's internal one,
+        which is refused while a Graph is capturing.  out as decode."""
+        ls, ns = self._log_slots(log_slots, "decrypt_slots")
+        _check_tensor(ct, "decrypt_slots: ct", (self.n,))
+        _check_tensor(sk, "decrypt_slots: sk", (self.n,))
+        if ct.dim() < 3 or ct.shape[-3] != 2:
+            raise ValueError(f"decrypt_slots: expected [..., 2, level, {self.n}], got "
+                             f"{tuple(ct.shape)}")
+        level = ct.shape[-2]
+        if not 1 <= level <= self.L:
+            raise ValueError(f"decrypt_slots: level must be in [1, {self.L}]")
+        if sk.dim() != 2 or sk.shape[0] < min(level, 2) or sk.device != ct.device:
+            raise ValueError(f"decrypt_slots: sk must be [L + K, {self.n}] on ct's device")
+        count = ct.numel() // (2 * level * self.n)
+        shape = (*ct.shape[:-3], ns)
+        if out is None:
+            out = _empty(shape, dtype=torch.complex128, device=ct.device)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.complex128 or \
+                    out.device != ct.device or not out.is_contiguous() or \
+                    tuple(out.shape) != shape:
+                raise ValueError(f"decrypt_slots: out must be a contiguous complex128 {shape} "
+                                 "tensor on ct's device")
+        with torch.cuda.device(self.device):
+            check(load().fhe_decrypt_slots(self._ptr, _ptr(out), _ptr(ct), _ptr(sk), float(delta),
+                                           ls, level, count, _ptr(workspace), _stream(ct)),
+                  "fhe_decrypt_slots")
+        return out
+
     def encode_diagonals(self, diags, n1: int, n2: int, delta, level=None, log_slots=None):
         """The plaintexts of a baby-step / giant-step matrix product from a slot matrix's
         diagonals: diags maps k < n1 n2 to the complex [N/2] vector d_k[j] = A[j][(j + k) mod N/2]

@@ -717,6 +717,28 @@ int fhe_decode_sparse(const fhe_ctx* ctx, double* slots, const uint64_t* pt, dou
                       uint32_t log_slots, uint32_t pt_rows, uint32_t level, uint32_t count,
                       void* workspace, fhe_stream_t stream);
 
+/* ---- Decrypt straight to slots: fhe_encrypt_slots' way back -------------------------------------
+ * ct [batch][2][level][N], NTT form, canonical residues, 1 <= level <= L; sk [L + K][N], of which
+ * only the rows l < min(level, 2) are read; slots [batch][2^log_slots][2] doubles,
+ * 0 <= log_slots <= log_n - 1 (log_n - 1: full packing).  The result is, bit for bit, that of
+ *   fhe_decrypt(pt, ct, sk, batch, level)   ("sampling, keys, encryption" above), then
+ *   fhe_decode_sparse(slots, pt, delta, log_slots, pt_rows = level, level, batch)
+ * ("Sparse packing" above; with log_slots = log_n - 1 that is fhe_decode): nothing new is defined.
+ * Only limb 0 of both components is read, and limb 1 when level >= 2, through the ciphertext's own
+ * strides; no [level][N] plaintext is formed (c0 + c1 s is computed by the inverse transform's
+ * first pass as it loads).
+ * FHE_EINVAL before any launch: a null context, slots, ct or sk; level 0 or above L;
+ * log_slots > log_n - 1; a delta that is not finite and positive; slots overlapping ct, sk (its
+ * first two rows) or the workspace passed; workspace == NULL while the stream is capturing.
+ * batch == 0 is a no-op.  Workspace: fhe_decode_workspace(ctx, batch) bytes; NULL = internal.
+ * Capture-safe with an explicit workspace: nothing is allocated, copied or synchronised.
+ * FHECORE_DECRYPT_UNFUSED=1 makes the call take the form of contexts with a modulus >= 2^61 (the
+ * product written out over the limbs read, then the whole inverse transform) on any context: the
+ * same bits. */
+int fhe_decrypt_slots(const fhe_ctx* ctx, double* slots, const uint64_t* ct, const uint64_t* sk,
+                      double delta, uint32_t log_slots, uint32_t level, uint32_t batch,
+                      void* workspace, fhe_stream_t stream);
+
 /* ---- HIP graphs: capture a sequence of libfhecore calls on `stream` and replay it -----------
  * Between fhe_graph_begin and fhe_graph_end every call that takes a workspace must be given an
  * explicit one: with workspace == NULL a call returns FHE_EINVAL while the stream is capturing

@@ -652,6 +652,27 @@ class Evaluator {
           "fhe_decode_sparse");
     return out;
   }
+  // Decrypt straight to slots (fhe_decrypt_slots): bit for bit decode(decrypt(ct, sk), delta,
+  // ct.limbs), without forming the plaintext -> N/2 complex doubles in a buffer of N words.
+  DeviceBuffer decrypt_slots(const Ciphertext& ct, const SecretKey& sk, double delta) const {
+    return decrypt_slots(ct, sk, delta, ctx_.log_n() - 1);
+  }
+  // The same for 2^log_slots slots (decode's sparse overload), in a buffer of 2^(log_slots + 1)
+  // words.
+  DeviceBuffer decrypt_slots(const Ciphertext& ct, const SecretKey& sk, double delta,
+                             uint32_t log_slots) const {
+    if (ct.components != 2 || !ct.ntt_form)
+      throw Error(FHE_EINVAL, "decrypt_slots: need an NTT-form ciphertext");
+    if (log_slots > ctx_.log_n() - 1)
+      throw Error(FHE_EINVAL, "decrypt_slots: log_slots must be in [0, log_n - 1]");
+    DeviceBuffer out((size_t)2 << log_slots);
+    const size_t need = fhe_decode_workspace(ctx_.get(), 1);
+    if (ws_.size() * 8 < need) ws_ = DeviceBuffer((need + 7) / 8);
+    check(fhe_decrypt_slots(ctx_.get(), reinterpret_cast<double*>(out.data()), ct.data(),
+                            sk.s.data(), delta, log_slots, ct.limbs, 1, ws_.data(), s_),
+          "fhe_decrypt_slots");
+    return out;
+  }
 
  private:
   std::vector<Ciphertext> encrypt_batch(const Ciphertext* pt, const DeviceBuffer* slots, double delta,
